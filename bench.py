@@ -2,11 +2,19 @@
 """bench.py — PixelPick hot path on MI355X: ONE JSON line per run (driver contract).
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 BASELINE.json metric: images/s of a full DeepLabv3+-MobileNetV2 train step + Mpixels/s of acquisition, at
-Cityscapes-quarter 256x512 (configs[1]).  One run measures both on synthetic data resident in HBM:
+Cityscapes-quarter 256x512 (configs[1]).  A plain run sets up, warms up, times the K steps of the headline leg (the train
+step; the acquisition with --mode acq) and prints the line: metric, value, unit, ms_per_step, dtype, higher_is_better and
+the train{} / acquisition{} record of that leg.  --dump-outputs DIR also writes what the headline leg computed in its last
+timed step as DIR/<name>.npy (float32 / float64, at most 64 MB; inputs are seeded, so runs with the same arguments are
+comparable output for output).  --full adds every other record below (acquisition{} too, under --mode both), the
+other BASELINE configurations, the distributed{} diagnostics and the checks against the oracle.  All on synthetic data
+resident in HBM:
 
   value / ms_per_step   K train steps (model.py:101-122: forward, sparse cross-entropy over 20 labelled
                         pixels/image, backward, [RCCL all-reduce of the flat gradient], Adam with the backbone
@@ -296,6 +304,32 @@ def _acq_source_hash():
     return h.hexdigest()
 
 
+DUMP_BUDGET_BYTES = 60 * 10 ** 6     # under the 64 MB a --dump-outputs directory may hold, .npy headers included
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write every named array (a torch tensor or a number) as out_dir/<name>.npy, float64 for integers and
+    float64 inputs, float32 otherwise.  When the arrays together exceed DUMP_BUDGET_BYTES, every array above 1 MB is replaced by
+    the same fixed, seeded sample of its flattened elements in every run, sized in proportion to the array (<name>.npy holds the
+    sampled values, <name>_index.npy their positions), so that two builds can be compared file for file."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, v in arrays.items():
+        t = v.detach().cpu() if torch.is_tensor(v) else torch.tensor(v)
+        host[name] = t.to(torch.float32 if t.dtype in (torch.float32, torch.float16, torch.bfloat16) else torch.float64).numpy()
+    total = sum(x.nbytes for x in host.values())
+    big = {name: x.nbytes for name, x in host.items() if x.nbytes > 10 ** 6}
+    room = DUMP_BUDGET_BYTES - (total - sum(big.values()))          # what the whole small arrays leave for the samples
+    for name, x in host.items():
+        if total > DUMP_BUDGET_BYTES and name in big:
+            n = int(room * x.nbytes // sum(big.values()) // (x.itemsize + 8))       # sampled values + their float64 positions
+            pos = np.sort(np.random.default_rng(0).choice(x.size, size=n, replace=False))
+            np.save(os.path.join(out_dir, f"{name}_index.npy"), pos.astype(np.float64))
+            x = x.reshape(-1)[pos]
+        np.save(os.path.join(out_dir, f"{name}.npy"), x)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -328,6 +362,13 @@ def main():
     ap.add_argument("--replay", default="auto", choices=["auto", "on", "off"],
                     help="re-issue the train step's recorded launch list (FlatTrainer.enable_replay: same GPU schedule, half the host "
                          "time per step).  auto: on when this process has fewer than 8 host cores per rank to enqueue from")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure as well: the acquisition leg of --mode both, rooflines, yardsticks, the "
+                         "replayed-step comparison, host enqueue cost, the distributed diagnostics, the other BASELINE configurations, "
+                         "the CPU baselines and the checks against the oracle.  Without it a run times the headline leg only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline leg computed in its last timed step as DIR/<name>.npy (rank 0): the train step's "
+                         "loss, parameters, gradients and BatchNorm buffers, or the acquisition's picks and their scores")
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -437,10 +478,12 @@ def main():
         cores_per_rank = (os.cpu_count() or 1) / max(world, 1)
         replay = a.replay == "on" or (a.replay == "auto" and cores_per_rank < 8)
         replay_why = "forced" if a.replay == "on" else ("fewer than 8 host cores per rank" if replay else None)
+        probe_rec = None
         if a.replay == "auto" and not replay:
             # probe (untimed, before the warmup): what a step costs the HOST when issued into empty queues against what it costs the
-            # GPU.  A host that needs more than 0.9 of the GPU step to enqueue it would bound the run on a busier or slower box than
-            # this one: take the recorded launch list then (about half the host cost, same GPU schedule, bit-identical steps).
+            # GPU.  It only informs (replay_probe, --full): the launch form follows from the arguments and the host-core count alone,
+            # so that runs with the same arguments compute the same steps (the replayed step draws its dropout masks from the device
+            # seed word and records two extra steps).  Its steps stay, so that the timed loop starts from the same state as ever.
             for _ in range(3):
                 tr.train_step(x, y)
             probe = []
@@ -456,11 +499,13 @@ def main():
             torch.cuda.synchronize(dev)
             gpu_step = max_over_ranks((time.perf_counter() - t) / 5)
             host_step = max_over_ranks(sorted(probe)[1])
-            if host_step > 0.9 * gpu_step:       # (the replayed step is ~1 % slower on the GPU: only when the host really is the limit)
-                replay, replay_why = True, f"host enqueue {host_step * 1e3:.2f} ms > 0.9 x step {gpu_step * 1e3:.2f} ms in the probe"
+            probe_rec = {"host_enqueue_ms": round(host_step * 1e3, 3), "gpu_step_ms": round(gpu_step * 1e3, 3),
+                         "host_bound": bool(host_step > 0.9 * gpu_step),
+                         "what": "one step issued into empty queues vs the step time, 3 + 3 + 5 untimed steps before the warmup; "
+                                 "host_bound: the replayed launch list (--replay on) may be faster on this host"}
         if replay:
             tr.enable_replay(x, y, warmup=1)         # recorded launch list, eager two-queue GPU schedule (bit-identical steps)
-        tr.time_collectives = dist is not None
+        tr.time_collectives = dist is not None and a.full       # (events around the all-reduces: the distributed{} record only)
         host_s = [0.0]
 
         def one_step():
@@ -473,16 +518,22 @@ def main():
         tr.__dict__["comm_times"] = []
         el = timed(one_step, steps, 0)
         host_loop_ms = max_over_ranks(host_s[0]) / steps * 1e3
-        # the enqueue cost proper: one step issued into EMPTY queues (in the loop above a host that runs ahead of the GPU is
-        # throttled by the full queue, so the in-loop figure tends to the GPU step time whatever the host costs)
-        solo = []
-        for _ in range(5):
+        if headline and a.dump_outputs and rank == 0:
+            bufs = [b.reshape(-1).float() for b in model.buffers() if b.dtype.is_floating_point]
+            dump_outputs(a.dump_outputs, {"loss": tr.last_loss, "params": tr.flat_p, "grads": tr.flat_g,
+                                          **({"buffers": torch.cat(bufs)} if bufs else {})})
+        host_ms = None
+        if a.full:
+            # the enqueue cost proper: one step issued into EMPTY queues (in the loop above a host that runs ahead of the GPU is
+            # throttled by the full queue, so the in-loop figure tends to the GPU step time whatever the host costs)
+            solo = []
+            for _ in range(5):
+                torch.cuda.synchronize(dev)
+                t = time.perf_counter()
+                tr.train_step(x, y)
+                solo.append(time.perf_counter() - t)
             torch.cuda.synchronize(dev)
-            t = time.perf_counter()
-            tr.train_step(x, y)
-            solo.append(time.perf_counter() - t)
-        torch.cuda.synchronize(dev)
-        host_ms = max_over_ranks(sorted(solo)[len(solo) // 2]) * 1e3
+            host_ms = max_over_ranks(sorted(solo)[len(solo) // 2]) * 1e3
         loss = float(tr.last_loss.item())
         native_plan = bool(replay and isinstance(tr._plan, _lib.NativePlan))
         n_launches = None
@@ -497,11 +548,15 @@ def main():
                             if replay else "eager") + ", small weight gradients on a second stream",
                  # host time spent inside train_step() per step (enqueue only, nothing synchronises): a host slower than the
                  # GPU step shows up HERE, not as an unexplained scaling loss
-                 "host_enqueue_ms_per_step": host_ms, "host_in_loop_ms_per_step": host_loop_ms, "replay": bool(replay),
+                 "host_in_loop_ms_per_step": host_loop_ms, "replay": bool(replay),
                  "replay_reason": replay_why, "launches_per_step": n_launches,
                  "host_cores_per_rank": round(cores_per_rank, 1),
                  "grad_bytes_allreduced_per_step": tr.n * 4 if world > 1 else 0}
-        if headline:
+        if host_ms is not None:
+            train["host_enqueue_ms_per_step"] = host_ms
+        if a.full and probe_rec is not None:
+            train["replay_probe"] = probe_rec
+        if headline and a.full:
             was_replay = tr._plan is not None
             if was_replay:
                 tr.disable_replay()
@@ -514,7 +569,7 @@ def main():
             cm["frac_if_floors_add"] = round((cm["mfma_floor_ms"] + cm["hbm_floor_ms"]) / train["ms_per_step"], 4)
             cm["achieved_TF_fp32_equivalent"] = round(cm["flops_per_step"] / (train["ms_per_step"] * 1e-3) / 1e12, 2)
             train["roofline"] = cm
-        if headline and not replay and dist is None:
+        if headline and a.full and not replay and dist is None:
             # the same step through the recorded launch list (native executor, csrc/plan.hip): what the host pays then, and what the GPU
             # step costs - reported beside the eager figures above, which stay the headline while they are the faster ones
             tr.enable_replay(x, y, warmup=1)
@@ -540,7 +595,7 @@ def main():
         from pixelpick_amd import engine as E
         TB = a.train_batch
         train, tr, model = train_leg(a.network, a.steps, a.warmup, H, W, C, headline=True)
-        if dist is not None:
+        if dist is not None and a.full:
             # what the communicator really is, and what the gradient exchange costs on its own (both buckets back to back,
             # nothing else running): the overlapped step hides most of the first bucket under the encoder backward
             ar = []
@@ -619,7 +674,7 @@ def main():
         # the depthwise layers of MobileNetV2 against the HBM roofline (north_star: "bandwidth-bound and justified against the HBM roofline";
         # SURVEY 8(d)): every depthwise call of the RECORDED step re-issued on its own with the step's arguments (pixelpick_amd/profiling.py;
         # the per-layer table with cold timings and copy yardsticks is tools/dw_bench.py -> profiles/r06_dw_layers.txt)
-        if world == 1 and a.network == "deeplab" and not a.no_other_configs:
+        if a.full and world == 1 and a.network == "deeplab" and not a.no_other_configs:
             from pixelpick_amd import profiling
             was_replay = tr._plan is not None
             if not was_replay:
@@ -631,6 +686,7 @@ def main():
                                               "what": "mobilenet_v2.py:38,52 - the 17 depthwise 3x3 layers of one train step (B = %d, %dx%d), each launch timed alone with the "
                                                       "step's own arguments, warm; bytes = every tensor once" % (TB, H, W),
                                               **profiling.depthwise_summary(rows_dw)}
+    if train is not None and a.full:
         # dominant train kernel vs the fp32 MFMA roofline: SegmentHead conv 3x3 304->256 on [TB,64,128] (decoders.py:107)
         Hq, Wq = H // 4, W // 4
         xa = torch.randn((TB, Hq, Wq, 304), device=dev)
@@ -789,6 +845,9 @@ def main():
         tr.disable_replay()
         del tr, model, xa, wa, ya
         torch.cuda.empty_cache()
+    elif train is not None:
+        tr.disable_replay()
+        del tr, model
 
     # ------------------------------------------------------------------------------------ acquisition
     def acq_leg(B, Ca, Ha, Wa, ka, strategy, layout, steps, warmup, headline):
@@ -809,16 +868,22 @@ def main():
             rc = L.pp_acq_score_topk(logits.data_ptr(), B, Ca, Ha, Wa, sB, sC, sH, sW, excl.data_ptr(), sid, ka,
                                      idx.data_ptr(), val.data_ptr(), None, ws.data_ptr(), ws.numel(), stream)
             _lib.check(rc, "pp_acq_score_topk")
-        ev = HipEvents(steps)
+        ev = HipEvents(steps) if a.full else None            # (the per-launch kernel times: the roofline{} record only)
         el = timed(acq_step, steps, warmup, ev)
+        acqr = {"value": round(du.whole_job_rate(B * Ha * Wa * steps, el, device=dev if dist is not None else None)[0] / 1e6, 1), "unit": "Mpixels/s",
+                "ms_per_step": round(el / steps * 1e3, 4), "images_per_launch_per_gpu": B, "k": ka,
+                "strategy": strategy, "layout": layout}
+        if headline and a.mode == "acq" and a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, {"picks": idx, "scores": val})
+        if ev is None:
+            del logits, excl, idx, val, ws
+            torch.cuda.empty_cache()
+            return acqr, None
         kms = ev.elapsed_ms()
         ev.destroy()
         alg_bytes = B * Ha * Wa * (4 * Ca + 1)               # per launch of acq_kernel on ONE GPU
         kavg = sum(kms) / len(kms)
         achieved = alg_bytes / (kavg * 1e-3) / 1e9
-        acqr = {"value": round(du.whole_job_rate(B * Ha * Wa * steps, el, device=dev if dist is not None else None)[0] / 1e6, 1), "unit": "Mpixels/s",
-                "ms_per_step": round(el / steps * 1e3, 4), "images_per_launch_per_gpu": B, "k": ka,
-                "strategy": strategy, "layout": layout}
         # HBM traffic per launch: a counter pass cannot run inside this process, so it comes from the record a committed
         # script writes (tools/measure_acq_traffic.py: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, FETCH doubled as
         # MI355X_MICROARCH.md prescribes for gfx950).  The record carries the hash of the kernel source it measured; if this
@@ -902,9 +967,11 @@ def main():
         return acqr, roof
 
     acqr = None
-    if a.mode in ("both", "acq"):
-        acqr, line["roofline"] = acq_leg(a.batch, C, H, W, k, a.strategy, a.layout, a.steps, a.warmup, True)
-        if not a.exact_formula and world == 1 and not a.no_other_configs:
+    if a.mode == "acq" or (a.mode == "both" and a.full):
+        acqr, roof = acq_leg(a.batch, C, H, W, k, a.strategy, a.layout, a.steps, a.warmup, True)
+        if roof is not None:
+            line["roofline"] = roof
+        if a.full and not a.exact_formula and world == 1 and not a.no_other_configs:
             # the reference's operation order as the scorer (SURVEY 7.4 wanted it selectable; the default is the algebraic form):
             # same launch, same traffic, more VALU work per pixel
             exact_flag[0] = 0x100
@@ -918,7 +985,7 @@ def main():
     # Bounded sub-records in the SAME run (N = 1 only; the scaling runs stay short): every acquisition shape / strategy the
     # BASELINE.json configs name plus the reference's default top-5 % mode (args.py:25), each with its own roofline of acq_kernel,
     # and the ResNet50 train steps of configs[2] (the reference's ResNet50 model FPNSeg, and DeepLabv3+-ResNet50 as named).
-    if a.mode == "both" and world == 1 and not a.no_other_configs and a.network == "deeplab" and (C, H, W) == (19, 256, 512):
+    if a.full and a.mode == "both" and world == 1 and not a.no_other_configs and a.network == "deeplab" and (C, H, W) == (19, 256, 512):
         others = []
         oc_steps, oc_warm = max(5, min(a.steps, 20)), 5
         for name, (Bo, Co, Ho, Wo, ko, so) in (
@@ -992,7 +1059,7 @@ def main():
         if acqr is not None:
             out["acquisition"] = acqr
         out.update(line)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             # torch's default of one intra-op thread per core (128 here) is the WORST setting for these ops on this
             # host (fork/join dominates: 0.96 img/s and 15 Mpix/s vs 5.7 and 146 at 16 threads, measured round 1), so the
             # port is timed at a few thread counts and the best one is the baseline; `cores` = the threads it used.

@@ -498,7 +498,7 @@ def test_bench_line_from_two_ranks_through_torch_distributed_run():
     env.pop("RANK", None), env.pop("WORLD_SIZE", None), env.pop("LOCAL_RANK", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--batch", "8", "--no-cpu-baseline"]
+           "--batch", "8", "--no-cpu-baseline", "--full"]
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -527,7 +527,7 @@ def test_bench_gpus_n_without_a_launcher_spawns_its_own_ranks(replay, ranks):
     # ranks = 8: the driver's `--gpus 8` line with eight ranks sharing this box's one GPU over gloo - plumbing only (nranks, buckets,
     # the global batch; the replayed step returns to Python for each of the three all-reduces)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ranks), "--steps", "3", "--warmup", "1", "--batch", "8",
-           "--no-cpu-baseline", "--mode", "train", "--replay", replay]
+           "--no-cpu-baseline", "--mode", "train", "--replay", replay, "--full"]
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]

@@ -3,7 +3,7 @@ cd $GRAFT_REPO_ROOT
 O=${1:-gpurun_out/acq_sweep}; mkdir -p $O
 run() { # name, args...
   n=$1; shift
-  python bench.py --mode acq --no-cpu-baseline --no-other-configs --steps 20 --warmup 5 "$@" 2>/dev/null | python -c "
+  python bench.py --full --mode acq --no-cpu-baseline --no-other-configs --steps 20 --warmup 5 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); r=d['roofline']; y=r['read_only_yardstick'] or {}
 print('$n | %s | %.1f Mpix/s | kernel ms %.4f | frac %.4f | yard %.4f' % (' '.join(sys.argv[1:]), d['value'], r['kernel_ms_avg'], r['frac'], y.get('frac_of_peak',0)))" "$@" >> $O/sweep.txt

@@ -176,6 +176,7 @@ KNOB_SIGNATURES = {
     "pp_debug_set_gemm_pw": (None, [_int]),
     "pp_debug_set_x3_variant": (None, [_int]),
     "pp_debug_occupy_cus": (_int, [_int, _p, _u64, _p, _p]),
+    "pp_debug_launch_log": (_int, [ctypes.c_char_p, _int]),
 }
 
 _lib = None

@@ -2,6 +2,10 @@
 #include "pp_common.h"
 
 #include <stdlib.h>
+#include <string.h>
+
+#include <mutex>
+#include <string>
 
 namespace pp {
 
@@ -19,6 +23,21 @@ int fail(int code, const char* fmt, ...)
     va_end(ap);
     return code;
 }
+
+#ifdef PP_DEBUG_KNOBS
+// launch log of the test build (pp_debug_launch_log): which kernel each dispatcher branch reached.  Bounded, so that a process that
+// never reads it (the rest of the suite) does not grow it without end: names past the bound are dropped.
+static std::mutex g_launch_log_mu;
+static std::string g_launch_log;
+
+void debug_log_launch(const char* what)
+{
+    std::lock_guard<std::mutex> lk(g_launch_log_mu);
+    if (g_launch_log.size() > (1u << 20)) return;
+    if (!g_launch_log.empty()) g_launch_log += ';';
+    g_launch_log += what;
+}
+#endif
 
 EventHook& event_hook()
 {
@@ -117,6 +136,21 @@ int pp_debug_occupy_cus(int blocks, const int* stop, uint64_t max_ticks, uint64_
     hipLaunchKernelGGL(pp::occupy_kernel, dim3((unsigned)blocks), dim3(1024), lds, reinterpret_cast<hipStream_t>(stream), stop,
                        (unsigned long long)max_ticks, reinterpret_cast<unsigned long long*>(started));
     return hipGetLastError() == hipSuccess ? PP_OK : pp::fail(PP_ERR_LAUNCH, "occupy_kernel launch failed");
+}
+#endif
+
+#ifdef PP_DEBUG_KNOBS
+int pp_debug_launch_log(char* buf, int n)
+{
+    std::lock_guard<std::mutex> lk(pp::g_launch_log_mu);
+    const int len = (int)pp::g_launch_log.size();
+    if (buf && n > 0) {
+        const int m = len < n - 1 ? len : n - 1;
+        memcpy(buf, pp::g_launch_log.data(), (size_t)m);
+        buf[m] = '\0';
+    }
+    pp::g_launch_log.clear();
+    return len;
 }
 #endif
 

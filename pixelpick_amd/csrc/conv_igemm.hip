@@ -3836,8 +3836,11 @@ static int launch_conv(const ConvParams& p_in, void* workspace, size_t ws_bytes,
             // profiles/r06_gemm_pw.txt - and loses to the implicit-GEMM kernel on wide, shallow problems)
             const bool bt_ok = !BWD || g_gemm_pw >= 2 || (p.Ck >= 512 && 2 * p.Ck >= p.Cn) || p.Cn <= 128;
             const int form = bt_ok ? gemm_pw_choose(p.M, p.Cn, p.Ck) : -1;
-            if (form >= 0 && gemm_pw_supported(p.x, p.ldx, p.w, p.Cout, p.y, p.ldy, p.M, p.Cn, p.Ck))
-                return launch_gemm_pw(p.x, p.ldx, p.w, p.Cout, p.bias, p.y, p.ldy, p.M, p.Cn, p.Ck, p.accumulate, form, g_conv_xcd_remap, st, BWD ? 1 : 0);
+            // the one live tap need not be weight tap 0: the centre tap of a strided backward-data phase (widx 4 of a 3x3) or of a
+            // dilation wider than the map (vec: Cin, Cout multiples of 4, so the tap's weights stay 16-byte aligned)
+            const float* w1 = p.w + (int64_t)p.taps.widx[0] * p.Cin * p.Cout;
+            if (form >= 0 && gemm_pw_supported(p.x, p.ldx, w1, p.Cout, p.y, p.ldy, p.M, p.Cn, p.Ck))
+                return launch_gemm_pw(p.x, p.ldx, w1, p.Cout, p.bias, p.y, p.ldy, p.M, p.Cn, p.Ck, p.accumulate, form, g_conv_xcd_remap, st, BWD ? 1 : 0);
         }
     }
     // few-row, deep-K pointwise layers: in-block split-K over wave-private LDS-DMA rings (conv1x1_ksplit_dma_kernel)
@@ -3929,6 +3932,7 @@ static int launch_conv(const ConvParams& p_in, void* workspace, size_t ws_bytes,
     p.ks_per_split = pl.ks_per_split;
     p.part = reinterpret_cast<float*>(workspace);
     dim3 grid((unsigned)pl.tiles, (unsigned)pl.splits);
+    const char* kname = "conv_igemm_kernel<128x32>";      // (the launch log of the test build tells the tile forms apart by these names)
     if (pl.cfg == 0) {
         if (vec) hipLaunchKernelGGL((conv_igemm_kernel<128, 32, 4, 1, BWD, true>), grid, dim3(kThreads), 0, st, p);
         else     hipLaunchKernelGGL((conv_igemm_kernel<128, 32, 4, 1, BWD, false>), grid, dim3(kThreads), 0, st, p);
@@ -3937,6 +3941,7 @@ static int launch_conv(const ConvParams& p_in, void* workspace, size_t ws_bytes,
             const bool dma_ok64 = vec && g_conv_dma && (!BWD || g_conv_dma == 1 || g_conv_dma == 3) && p.taps.n <= 32 && (!BWD || p.bwd_stride <= 1) &&
                                   (int64_t)p.B * p.H * p.W * p.ldx < (1ll << 31) - (1ll << 24) &&
                                   (int64_t)kMaxTaps * p.Cin * p.Cout < (1ll << 31);
+            kname = dma_ok64 ? "conv_igemm_dma_kernel<128x64>" : "conv_igemm_kernel<128x64>";
             if (dma_ok64) hipLaunchKernelGGL((conv_igemm_dma_kernel<128, 64, BWD>), grid, dim3(kThreads), 0, st, p);
             else
             if (vec) hipLaunchKernelGGL((conv_igemm_kernel<128, 64, 2, 2, BWD, true>), grid, dim3(kThreads), 0, st, p);
@@ -3945,23 +3950,27 @@ static int launch_conv(const ConvParams& p_in, void* workspace, size_t ws_bytes,
             const bool dma_ok = vec && g_conv_dma && (!BWD || g_conv_dma == 1) && p.taps.n <= 32 && (!BWD || p.bwd_stride <= 1) &&
                                 (int64_t)p.B * p.H * p.W * p.ldx < (1ll << 31) - (1ll << 24) &&
                                 (int64_t)kMaxTaps * p.Cin * p.Cout < (1ll << 31);
+            kname = dma_ok ? "conv_igemm_dma_kernel<128x128>" : "conv_igemm_kernel<128x128>";
             if (dma_ok) hipLaunchKernelGGL((conv_igemm_dma_kernel<128, 128, BWD>), grid, dim3(kThreads), 0, st, p);
             else if (vec) hipLaunchKernelGGL((conv_igemm_kernel<128, 128, 2, 2, BWD, true>), grid, dim3(kThreads), g_conv_lds_pad, st, p);
             else     hipLaunchKernelGGL((conv_igemm_kernel<128, 128, 2, 2, BWD, false>), grid, dim3(kThreads), g_conv_lds_pad, st, p);
         }
     } else if (pl.cfg == 4) {
+        kname = "conv_igemm_kernel<128x128 bk32>";
         hipLaunchKernelGGL((conv_igemm_kernel<128, 128, 2, 2, BWD, true, 32>), grid, dim3(kThreads), 0, st, p);
     } else if (pl.cfg == 3) {
+        kname = "conv_igemm_kernel<64x64 bk64>";
         hipLaunchKernelGGL((conv_igemm_kernel<64, 64, 2, 2, BWD, true, 64>), grid, dim3(kThreads), 0, st, p);
     } else {
         const bool dma_ok = vec && g_conv_dma64 && (!BWD || g_conv_dma64 == 1) && p.taps.n <= 32 && (!BWD || p.bwd_stride <= 1) &&
                             (int64_t)p.B * p.H * p.W * p.ldx < (1ll << 31) - (1ll << 24) &&
                             (int64_t)kMaxTaps * p.Cin * p.Cout < (1ll << 31);
+        kname = dma_ok ? "conv_igemm_dma_kernel<64x64>" : "conv_igemm_kernel<64x64>";
         if (dma_ok)   hipLaunchKernelGGL((conv_igemm_dma_kernel<64, 64, BWD>), grid, dim3(kThreads), 0, st, p);
         else if (vec) hipLaunchKernelGGL((conv_igemm_kernel<64, 64, 2, 2, BWD, true>), grid, dim3(kThreads), 0, st, p);
         else          hipLaunchKernelGGL((conv_igemm_kernel<64, 64, 2, 2, BWD, false>), grid, dim3(kThreads), 0, st, p);
     }
-    if (int rc = check_launch("conv_igemm_kernel")) return rc;
+    if (int rc = check_launch(kname)) return rc;
     if (pl.splits > 1 && p.stats) {
         const int64_t rpb = splitk_stats_rows_per_block(p.M);
         hipLaunchKernelGGL(splitk_reduce_stats_kernel, dim3((unsigned)cdiv(p.M, rpb)), dim3(256), 0, st, p.part, pl.splits, p.M, p.Cn,
@@ -4116,6 +4125,7 @@ static int launch_wgrad_narrow(WgradParams p, int kh, int kw, float* dw, float* 
     if (nt != kh * kw)
         if (hipMemsetAsync(dw, 0, (size_t)kh * kw * cn * 4, st) != hipSuccess) return fail(PP_ERR_LAUNCH, "conv bwd_weight: memset failed");
     dim3 grid((unsigned)nblk), blk(256);
+    const char* kname = stem ? "wgrad_stem3x3s2_kernel" : stem7 ? "wgrad_stem7x7s2_kernel" : form == 1 ? "wgrad_narrow_in_kernel" : "wgrad_narrow_out_kernel";
     if (stem) {
         hipLaunchKernelGGL((wgrad_stem3x3s2_kernel<4>), grid, blk, 0, st, p, rows_per_split);
         splits = nblk;                                    // one slice of partial sums per block from here on
@@ -4140,7 +4150,7 @@ static int launch_wgrad_narrow(WgradParams p, int kh, int kw, float* dw, float* 
         else if (p.Cout == 24)  hipLaunchKernelGGL((wgrad_narrow_out_kernel<24, 4>), grid, blk, 0, st, p, NL, RL, rows_per_split);
         else                    hipLaunchKernelGGL((wgrad_narrow_out_kernel<32, 4>), grid, blk, 0, st, p, NL, RL, rows_per_split);
     }
-    if (int rc = check_launch("wgrad_narrow_kernel")) return rc;
+    if (int rc = check_launch(kname)) return rc;
     if (reduce_deferrable(job, p.taps, cn, splits, dbias)) {
         fill_reduce_job(job, 2, p.part, dw, cn, splits, p.taps);
         *bias_done = true;                   // (no bias gradient asked for)
@@ -5025,6 +5035,7 @@ static int conv2d_bwd_weight_impl(const float* x, int64_t ldx, int B, int H, int
     }
     // LDS-DMA kernels: vector operands, no fused bias gradient, 32-bit safe row pitch; bits of g_wgrad_dma: 1 = 128-wide tiles, 2 = 64x64
     const bool dma = vec && p.bias_part == nullptr && (int64_t)p.M * std::max(ldx, lddy) < (1ll << 40);
+    const char* kname = "conv_wgrad_kernel";
     {
         if (use_x3) {
             uint16_t* xw_ = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(workspace) + x3_off);
@@ -5043,14 +5054,17 @@ static int conv2d_bwd_weight_impl(const float* x, int64_t ldx, int B, int H, int
                           (uint32_t)(rows_x * 32), (uint32_t)(p.M * 32)};
             dim3 gx((unsigned)(cdiv(Cin, 128) * p.taps.n), (unsigned)cdiv(Cout, 128), (unsigned)splits);
             hipLaunchKernelGGL((conv_wgrad_x3_kernel<128>), gx, dim3(kThreads), 0, st, p, o);
+            kname = "conv_wgrad_x3_kernel";
             goto reduce_partials;
         }
     }
     if (dma && (g_wgrad_dma & 1) && big && !(narrow_m && narrow_n)) {
+        kname = "conv_wgrad_dma_kernel";
         if (narrow_m)      hipLaunchKernelGGL((conv_wgrad_dma_kernel<64, 128>), grid, dim3(kThreads), 0, st, p);
         else if (narrow_n) hipLaunchKernelGGL((conv_wgrad_dma_kernel<128, 64>), grid, dim3(kThreads), 0, st, p);
         else               hipLaunchKernelGGL((conv_wgrad_dma_kernel<128, 128>), grid, dim3(kThreads), 0, st, p);
     } else if (dma && (g_wgrad_dma & 2) && (!big || (narrow_m && narrow_n))) {
+        kname = "conv_wgrad_dma_kernel<64x64>";
         hipLaunchKernelGGL((conv_wgrad_dma_kernel<64, 64>), grid, dim3(kThreads), 0, st, p);
     } else
     if (big && narrow_m && narrow_n) {
@@ -5070,7 +5084,7 @@ static int conv2d_bwd_weight_impl(const float* x, int64_t ldx, int B, int H, int
         else     hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, 2, 2, false>), grid, dim3(kThreads), g_wgrad_lds_pad, st, p);
     }
 reduce_partials:
-    if (int rc = check_launch("conv_wgrad_kernel")) return rc;
+    if (int rc = check_launch(kname)) return rc;
     const int64_t cn = (int64_t)Cin * Cout;
     if (p.counters) {                         // the launch reduced its own slices (wgrad_fold_tail)
         if (job) job->kind = 0;

@@ -374,7 +374,7 @@ int launch_gemm_pw(const float* a, int64_t lda, const float* b, int64_t ldb, con
             default: hipLaunchKernelGGL((gemm_pw_kernel<1, 1, 2, 2, 64>), grid, block, 0, st, p); break;
         }
     }
-    return hipGetLastError() == hipSuccess ? PP_OK : fail(PP_ERR_LAUNCH, "gemm_pw_kernel launch failed");
+    return check_launch("gemm_pw_kernel");
 }
 
 // element offsets are 32-bit, loads are 16-byte

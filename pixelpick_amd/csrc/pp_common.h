@@ -17,8 +17,16 @@ int fail(int code, const char* fmt, ...);
 
 inline hipStream_t as_stream(pp_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
+#ifdef PP_DEBUG_KNOBS
+// test build: the names of the kernels launched since the last pp_debug_launch_log() call (host side only)
+void debug_log_launch(const char* what);
+#endif
+
 inline int check_launch(const char* what)
 {
+#ifdef PP_DEBUG_KNOBS
+    debug_log_launch(what);
+#endif
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(PP_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
     return PP_OK;

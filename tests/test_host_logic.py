@@ -35,6 +35,32 @@ def _exported(path):
     return set(re.findall(r" T (pp_[a-z0-9_]+)", out)), out
 
 
+def _dispatch_kernel_names():
+    """Every kernel name the convolution dispatcher can put in the test build's launch log: the literal check_launch("...") names of
+    csrc/conv_igemm.hip and csrc/gemm_pw.hip, and the names assigned to `kname` where one check covers several tile forms."""
+    names = set()
+    for src in ("conv_igemm.hip", "gemm_pw.hip"):
+        txt = open(os.path.join(ROOT, "pixelpick_amd", "csrc", src)).read()
+        names |= set(re.findall(r'check_launch\("([^"]+)"\)', txt))
+        for stmt in re.findall(r"\bkname\s*=\s*([^;]+);", txt):
+            names |= set(re.findall(r'"([^"]+)"', stmt))
+    return names
+
+
+def test_every_conv_dispatch_kernel_has_a_test():
+    """Coverage ratchet: each kernel the dispatcher can launch is reached by a row of tests/test_conv_dispatch_gpu.py (EXPECTED, which
+    the GPU test holds to the union of what the rows log) or is listed in ELSEWHERE with the test that covers it.  A new dispatcher
+    branch without a row fails here."""
+    import test_conv_dispatch_gpu as td
+    names = _dispatch_kernel_names()
+    assert {"gemm_pw_kernel", "conv_igemm_dma_kernel<64x64>", "bwd_phase_interleave_kernel", "wgrad_stem7x7s2_kernel"} <= names
+    assert not (td.EXPECTED & set(td.ELSEWHERE))
+    uncovered = names - td.EXPECTED - set(td.ELSEWHERE)
+    assert not uncovered, f"dispatcher kernels without a test: {sorted(uncovered)}"
+    stale = (td.EXPECTED | set(td.ELSEWHERE)) - names
+    assert not stale, f"listed kernels the dispatcher no longer launches: {sorted(stale)}"
+
+
 def test_abi_exports_every_declared_symbol():
     """The PRODUCT library exports exactly include/pixelpick_hip.h and not one planner switch (no global mutable
     state behind the ABI); the TEST BUILD adds exactly include/pixelpick_hip_knobs.h."""

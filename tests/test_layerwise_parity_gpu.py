@@ -113,6 +113,17 @@ def test_fpn_every_layer_forward_and_backward_matches_oracle():
     assert sum(f for f, _ in lp.flips.values()) <= 2, lp.flips
 
 
+def test_fpn_every_layer_at_the_benchmark_shape():
+    """bench.py --network FPN: 256x512, batch 2.  The strided backward-data phases reach the pointwise GEMM only here (layer2.0.conv2's
+    centre-tap phase has 2 x 32 x 64 rows); at 64x96 no phase has 4096 rows."""
+    lp, loss, o_loss, m, o = _run("FPN", 19, 19, 2, 256, 512, 20, key="base")
+    assert abs(loss - o_loss) <= 1e-5 * max(1.0, abs(o_loss))
+    _assert_tight(lp, 213)
+    # 21x the activation units of the 64x96 case: at most one branch flip per 10^7 units (measured 6 of 1.56e8)
+    units = sum(u for _, u in lp.flips.values())
+    assert sum(f for f, _ in lp.flips.values()) <= max(2, units // 10**7), lp.flips
+
+
 def test_deeplab_r50_every_layer_forward_and_backward_matches_oracle():
     """The assembled DeepLabv3+-ResNet50 (SURVEY.md 0.1 extra): dilated ResNet50 + ASPP at output stride 8 (rates 12/24/36) +
     SegmentHead, every layer against the oracle of the same assembly (itself pinned to the reference's parts)."""

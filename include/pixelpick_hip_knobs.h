@@ -40,6 +40,11 @@ void pp_debug_set_bn_bytes_per_block(int bytes);   /* large maps: one block per 
 /* Debug: pp_bn_train_fwd_fused writes per-block wall-clock stamps (100 MHz; [blocks][8]: entry, statistics pass done, block
  * reduction done, partial published, strip combined, rows written) into this device buffer; NULL (default) = off. */
 void pp_debug_set_bn_probe(void* device_buffer);
+/* Debug: the list select of the large-k acquisition without a caller's map (topk_lsel_kernel) writes one uint32 per image
+ * (buffer[image], so the buffer holds at least B words) saying how that image was finished: 0 from the candidate lists, 1 redone in
+ * the kernel (the sample misled, or the candidates did not fit) and finished by the quantised select on the rewritten score map,
+ * 2 redone and finished by the radix select.  Calls that do not take the list route write nothing.  NULL (default) = off. */
+void pp_debug_set_lsel_probe(void* device_buffer);
 void pp_debug_set_conv_thresholds(int v);   /* big_tile_min | wgrad_rows_min << 12 (defaults 384 / 128) */
 void pp_debug_conv_plan(int64_t M, int Cn, int Ck, int ntaps, int* out4);   /* tile rows, tile cols, tiles, split-K slices */
 void pp_debug_set_conv_rows(int bits);      /* whole-row VALU kernels of the narrow pointwise layers: bit 0 off, bit 1 forward rows kernel only from 65536 rows (A/B) */

@@ -166,6 +166,7 @@ KNOB_SIGNATURES = {
     "pp_debug_set_bn_target": (None, [_int]),
     "pp_debug_set_bn_bytes_per_block": (None, [_int]),
     "pp_debug_set_bn_probe": (None, [_p]),
+    "pp_debug_set_lsel_probe": (None, [_p]),
     "pp_debug_set_conv_thresholds": (None, [_int]),
     "pp_debug_conv_plan": (None, [_i64, _int, _int, _int, _p]),
     "pp_debug_set_conv_variant": (None, [_int]),

@@ -1666,10 +1666,22 @@ __device__ __forceinline__ uint32_t lbin(uint32_t key, bool lg, float tv, float 
 // redone exactly by its own block, right here: the score map of the image - the default scorer's arithmetic, written over the image's own,
 // by then consumed, list segments - and the one-block radix select on it.  Slow (one block scores 10 MB of logits) and rare; nothing is
 // launched for it, so the usual case pays nothing (two idle launches - a map kernel over a flagged list and topk_large_kernel - cost 9 us).
+// Test build only (pp_debug_set_lsel_probe): one word per image saying how the image was finished - 0 from the lists, 1 redone and finished by
+// the quantised select on the rewritten map, 2 redone and finished by the radix select.  The product's kernel has no such parameter.
+#ifdef PP_DEBUG_KNOBS
+#define PP_LSEL_PROBE_PARAM , uint32_t* probe
+#define PP_LSEL_PROBE_ARG , g_lsel_probe
+#define PP_LSEL_PROBE(how) do { if (probe && threadIdx.x == 0) probe[blockIdx.x] = (how); } while (0)
+static uint32_t* g_lsel_probe = nullptr;
+#else
+#define PP_LSEL_PROBE_PARAM
+#define PP_LSEL_PROBE_ARG
+#define PP_LSEL_PROBE(how) do { } while (0)
+#endif
 template <int CMAX>
 __global__ __launch_bounds__(kLargeThreads) void topk_lsel_kernel(AcqParams p, const uint64_t* list, const uint32_t* cnt, const uint32_t* tkey,
                                                                  int64_t eimg, int nseg, int segsz, int k, int largest, float range,
-                                                                 int32_t* out_idx, float* out_val)
+                                                                 int32_t* out_idx, float* out_val PP_LSEL_PROBE_PARAM)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint64_t* buf = reinterpret_cast<uint64_t*>(smem);                                   // kQCap candidates, grouped by bin
@@ -1819,6 +1831,7 @@ __global__ __launch_bounds__(kLargeThreads) void topk_lsel_kernel(AcqParams p, c
         }
         if (misc[3] && misc[1] <= (uint32_t)kQCap && !misc[2]) {     // block-uniform
             const uint32_t tb2 = misc[0], cnt2 = misc[1];
+            PP_LSEL_PROBE(1u);
             for (int64_t pix = tid; pix < p.N; pix += kLargeThreads) {
                 const float sc = fmap[pix];
                 const uint32_t q = qbin(sc, lg, qscale);
@@ -1839,6 +1852,7 @@ __global__ __launch_bounds__(kLargeThreads) void topk_lsel_kernel(AcqParams p, c
             return;
         }
         __syncthreads();
+        PP_LSEL_PROBE(2u);
         uint32_t* rh = reinterpret_cast<uint32_t*>(smem);                           // 256 + 64 words, then P 64-bit words (P <= 8192: k <= 7281)
         int P = 1;
         while (P < k) P <<= 1;
@@ -1846,6 +1860,7 @@ __global__ __launch_bounds__(kLargeThreads) void topk_lsel_kernel(AcqParams p, c
                         out_val ? out_val + (int64_t)img * k : nullptr);
         return;
     }
+    PP_LSEL_PROBE(0u);
     sweep(!one_chunk, [&](uint64_t w) {
         const uint32_t q = lbin((uint32_t)(w >> 32), lg, tv, lscale);
         if (q >= tb) buf[start[q] + atomicAdd(&hist[q], 1u)] = w;
@@ -2298,7 +2313,7 @@ static int run_emit_select(AcqParams p, const Plan& pl, int64_t B, int64_t k, in
     if (int rc = check_launch("acq_sample_thr_kernel")) return rc;
     if (int rc = dispatch_acq(q, pl, B, st)) return rc;
     PP_BY_C(topk_lsel_kernel, sgrid, lblock, kLSelLds, q, (const uint64_t*)q.elist, (const uint32_t*)ecnt, (const uint32_t*)tkey, q.eimg, q.nseg,
-            segsz, (int)k, largest, range, out_idx, out_val);
+            segsz, (int)k, largest, range, out_idx, out_val PP_LSEL_PROBE_ARG);
 #undef PP_BY_C
     return check_launch("topk_lsel_kernel");
 }
@@ -2468,6 +2483,10 @@ void pp_debug_set_reduce_mode(int mode)
 
 #ifdef PP_DEBUG_KNOBS
 void pp_debug_set_exact_formula(int on) { g_exact_formula = on ? 1 : 0; }
+#endif
+
+#ifdef PP_DEBUG_KNOBS
+void pp_debug_set_lsel_probe(void* device_buffer) { g_lsel_probe = reinterpret_cast<uint32_t*>(device_buffer); }
 #endif
 
 #ifdef PP_DEBUG_KNOBS

@@ -5,6 +5,7 @@ import os
 import numpy as np
 import pytest
 
+import acq_top5_cases as tc
 from oracle import acq as orc
 
 STRATS = ["entropy", "least_confidence", "margin_sampling"]
@@ -174,3 +175,91 @@ def test_blur_oracle_equals_cv2_fixture(golden_dir):
     for ks, sg, seed, ref in zip(g["ksize"], g["sigma"], g["seed"], g["blurred"]):
         got = aug.gaussian_blur(image(int(seed)), int(ks), float(sg))
         assert np.array_equal(got, ref), (int(ks), float(sg), str(g["cv2_version"]), int(np.abs(got.astype(int) - ref).max()))
+
+
+# ---------------------------------------------------------------- the top-5 % tests' own tools (tests/acq_top5_cases.py)
+@pytest.mark.parametrize("st", STRATS)
+def test_graded_builder_guard_and_checkers_that_can_fail(st):
+    """The graded 19 x 256 x 512 case (k = 6553) builds with its guard (>= 4 tol between the k + 1 leading oracle scores, picks =
+    planted spots in order: asserted inside the builder); both checkers accept the oracle's own picks and REJECT two adjacent ranks
+    swapped, one pick replaced by the best unselected pixel, and one value off by 3 tol - each by the rule that is there for it."""
+    C, H, W, k = 19, 256, 512, 6553
+    gi = tc.graded_image(C, H, W, st, k, 1)
+    assert gi["min_gap_tol"] >= tc.GUARD_TOLS and len(gi["spots"]) == k + tc.EXTRA
+    largest = tc.largest_of(st)
+    o_map = orc.apply_exclude(orc.score_map(gi["logits"], st), gi["excl"], st)
+    o_idx, o_val = gi["o_idx"], gi["o_val"]
+
+    def rules(idx, val):
+        v, info = tc.rank_tolerant_violations(idx, val, o_map, gi["excl"], k, largest)
+        return sorted({m.split(":")[0] for m in v}), info
+
+    got, info = rules(o_idx, o_val)
+    assert got == [] and info["strict_share"] == 1.0 and info["equal_share"] == 1.0
+    assert tc.exact_rank_violations(o_idx, o_val, o_idx, o_val) == []
+    r = k // 3
+    # (i) two adjacent ranks swapped, values travelling with their pixels: the order is wrong, nothing else
+    idx, val = o_idx.copy(), o_val.copy()
+    idx[[r, r + 1]], val[[r, r + 1]] = idx[[r + 1, r]], val[[r + 1, r]]
+    assert rules(idx, val)[0] == ["rule 3", "rule 5"]
+    assert [m.split(":")[0] for m in tc.exact_rank_violations(idx, val, o_idx, o_val)] == ["idx", "val"]
+    # (ii) one pick replaced by the best unselected pixel (with that pixel's own score)
+    best_unselected = int(gi["spots"][k])
+    idx, val = o_idx.copy(), o_val.copy()
+    idx[r], val[r] = best_unselected, o_map.reshape(-1)[best_unselected]
+    assert rules(idx, val)[0] == ["rule 3", "rule 4", "rule 5"]
+    assert tc.exact_rank_violations(idx, val, o_idx, o_val)
+    # the same at the last rank: no better pixel is missing, the k-th order statistic is 6 tol off
+    idx, val = o_idx.copy(), o_val.copy()
+    idx[k - 1], val[k - 1] = best_unselected, o_map.reshape(-1)[best_unselected]
+    assert rules(idx, val)[0] == ["rule 3", "rule 5"]
+    # (iii) one value off by 3 tol
+    val = o_val.copy()
+    val[r] = np.float32(val[r] + 3 * tc.tol(val[r]))
+    assert rules(o_idx, val)[0] == ["rule 2"]
+    assert [m.split(":")[0] for m in tc.exact_rank_violations(o_idx, val, o_idx, o_val)] == ["val"]
+    # (iv) a repeated pick, an excluded pick
+    idx = o_idx.copy()
+    idx[r] = idx[r + 2]
+    assert "rule 1" in rules(idx, o_val)[0]
+    idx = o_idx.copy()
+    idx[r] = int(np.flatnonzero(gi["excl"].reshape(-1))[0])
+    assert "rule 1" in rules(idx, o_val)[0]
+
+
+def test_rank_tolerant_checker_on_natural_data():
+    """Unshaped data: the rules hold for the oracle itself, rule 5 covers only the ranks that ARE separated (a small share), and a
+    swap of two ranks the oracle separates by less than 2 tol is accepted while a swap across a separated rank is not."""
+    rng = np.random.RandomState(3)
+    C, H, W, k = 19, 128, 256, 1638
+    logits = (rng.randn(1, C, H, W) * 3).astype(np.float32)
+    excl = (rng.rand(1, H, W) < 0.05).astype(np.uint8)
+    o_idx, o_val, o_map = orc.score_topk(logits, excl, "entropy", k, want_map=True)
+    o_map = orc.apply_exclude(o_map, excl, "entropy")
+    v, info = tc.rank_tolerant_violations(o_idx[0], o_val[0], o_map, excl, k, True)
+    assert v == [] and 0.0 < info["strict_share"] < 0.9
+    gap = np.abs(np.diff(o_val[0].astype(np.float64))) / tc.tol(o_val[0][:-1].astype(np.float64))
+    near, far = int(np.argmin(gap)), int(np.argmax(gap))
+    assert gap[near] < 1.0 and gap[far] > 4.0
+    for r, ok in ((near, True), (far, False)):
+        idx, val = o_idx[0].copy(), o_val[0].copy()
+        idx[[r, r + 1]], val[[r, r + 1]] = idx[[r + 1, r]], val[[r + 1, r]]
+        assert (tc.rank_tolerant_violations(idx, val, o_map, excl, k, True)[0] == []) == ok, (r, gap[r])
+
+
+@pytest.mark.parametrize("st", STRATS)
+def test_top5_default_fixture_order(golden_dir, st):
+    """tests/golden/acq_top5_default.npz (the reference's default call, top 5 % then 10 drawn): on the rebuilt logits the oracle
+    reproduces the reference's value-sorted 5 % order for every rank, its guard holds on the oracle's map too, and the drawn
+    coordinates are query.py:63-64's np.random.choice of that order."""
+    g = np.load(os.path.join(golden_dir, "acq_top5_default.npz"))
+    logits, prev, ys, excl, names, k = tc.rebuild_top5_default(g, st)
+    assert k == 819 and logits.shape == (2, 19, 128, 128) and all(p.any() for p in prev) and (ys == 19).any()
+    o_idx, o_val, o_map = orc.score_topk(logits, excl, st, k, want_map=True)
+    np.random.seed(int(g["np_seed"]))
+    for i in range(2):
+        assert o_idx[i].tolist() == g[f"{st}_order"][i].tolist()
+        gaps = tc.leading_gaps_in_tol(orc.apply_exclude(o_map[i], excl[i], st), k, tc.largest_of(st))
+        assert gaps.min() >= tc.GUARD_TOLS
+        sub = np.sort(np.random.choice(o_idx[i].astype(np.int64), 10, False))
+        assert sub.tolist() == np.sort(g[f"{st}_y_coords_{i}"] * 128 + g[f"{st}_x_{i}"]).tolist()

@@ -1,8 +1,9 @@
 """The suite runs on the TEST BUILD (tests/conftest.py: libpixelpick_hip_knobs.so, the product's sources + -DPP_DEBUG_KNOBS, because
 the parity tests force kernel forms through the pp_debug_* planner switches).  This file holds the PRODUCT library
 (libpixelpick_hip.so: include/pixelpick_hip.h and nothing else) to the same results: one script, run in a process of its own on each
-build - acquisition (query.py:190-204,57-61; three strategies, default and reference-order scorer, k = 20 and the top-5 % mode) and
-three DeepLabv3+-MNv2 train steps (model.py:101-122) - must print identical digests."""
+build - acquisition (query.py:190-204,57-61; three strategies, default and reference-order scorer, k = 20 and the top-5 % mode with a
+map at 96 x 160, and the top-5 % mode WITHOUT a map at 256 x 512, whose picks each process also holds to the CPU oracle's at every
+rank) and three DeepLabv3+-MNv2 train steps (model.py:101-122) - must print identical digests."""
 import os
 import subprocess
 import sys
@@ -33,6 +34,20 @@ for st in ("entropy", "least_confidence", "margin_sampling"):
         for k in (20, 768):
             idx, val, m = acq.score_topk(logits, excl, st, k, return_map=True, reference_order=ro)
             put(idx); put(val); put(m)
+# the top-5 %% call as QuerySelector makes it (no map, k = 5 %% of 256 x 512: for the default scorer the candidate-list route, which a
+# call that asks for the map never takes) on the graded cases of tests/acq_top5_cases.py: into the digest, and - the oracle library
+# travels with the tree - idx against the ORACLE'S picks at every rank, val within the score tolerance, in this process
+import acq_top5_cases as tc
+for st in tc.STRATS:
+    g_logits, g_excl, o_idx, o_val = tc.graded_case(19, 256, 512, st, 6553, 3)
+    for ro in (False, True):
+        idx, val, m = acq.score_topk(torch.from_numpy(g_logits).cuda(), torch.from_numpy(g_excl), st, 6553, reference_order=ro)
+        assert m is None
+        put(idx); put(val)
+        for b in range(3):
+            bad = tc.exact_rank_violations(idx[b].cpu().numpy(), val[b].cpu().numpy(), o_idx[b], o_val[b])
+            assert not bad, (st, ro, b, bad)
+print("TOP5 graded picks equal the oracle's")
 from pixelpick_amd.networks.layers import Dropout
 from pixelpick_amd.trainer import FlatTrainer
 from pixelpick_amd.utils.utils import get_model
@@ -57,6 +72,7 @@ def _run(knobs: str) -> str:
     env = dict(os.environ, PIXELPICK_KNOBS_BUILD=knobs, PIXELPICK_MNV2_WEIGHTS="random")
     out = subprocess.run([sys.executable, "-c", SCRIPT], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
+    assert "TOP5 graded picks equal the oracle's" in out.stdout, out.stdout[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("DIGEST ")]
     assert len(line) == 1, out.stdout[-2000:]
     return line[0]

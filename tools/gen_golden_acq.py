@@ -13,6 +13,7 @@ Reference call sites exercised:
   query.py:320-351   merge_previous_query_files                                       (G5)
   deeplab.py:55-56 + query.py:190   low-res logits -> interpolate -> crop -> score  (--lowres, §8f-1)
   networks/model.py:6-14 + decoders.py:57-77 + query.py:144-221   FPNSeg-ResNet50 acquisition round (--fpn)
+  args.py:24-27 + query.py:144-221,36,57-64   the default call: top 5 % by value, then 10 drawn (--top5)
 """
 import os
 import sys
@@ -499,6 +500,77 @@ def gen_random():
     print("random written")
 
 
+def gen_top5_default():
+    """The reference's DEFAULT acquisition call (args.py:24-27: top_n_percent = 0.05, n_pixels_by_us = 10) through
+    QuerySelector.__call__ (query.py:144-221,36,57-64) for the three score strategies: C = 19, two images of 128 x 128 (k = 819: the
+    smallest size at which the build selects from candidate lists instead of a score map), previous queries and void labels.
+    The images ARE the logits: the graded cases of tests/acq_top5_cases.py (every one of the k + 1 leading scores >= 4 tol from its
+    neighbours, asserted here on the REFERENCE's map) go through OneConv with an identity 1x1 weight and zero bias, which is exact.
+    Stored: what rebuilds the inputs (the base image is np.random.RandomState(seed) output, see acq_top5_cases.random_base; the
+    shaping is the rivals mask, the planted spots and their logit), the reference's value-sorted 5 % order per image, the drawn
+    coordinates with the numpy seed, and the query statistics."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    import acq_top5_cases as tc
+    C, h, w, n_img, np_seed = 19, 128, 128, 2, 2468
+    k = int(h * w * 0.05)
+    out = {"meta": np.array([C, h, w, n_img, k], dtype=np.int64), "np_seed": np.int64(np_seed)}
+    names = [f"/data/top5_{i:03d}.png" for i in range(n_img)]
+    out["names"] = np.array(names)
+    model = OneConv(torch.eye(C).reshape(C, C, 1, 1), torch.zeros(C))
+    for si, st in enumerate(STRATS):
+        largest = st in ["entropy", "least_confidence"]
+        xs, ys, prev, orders = [], [], [], []
+        for i in range(n_img):
+            seed = 500 + 10 * si + i
+            gi = tc.graded_image(C, h, w, st, k, seed)
+            rng = np.random.RandomState(seed + 7000)
+            excl = gi["excl"][0].astype(bool)
+            q = excl & (rng.rand(h, w) < 0.5)                       # previous queries; the rest of the exclusion is void
+            y = rng.randint(0, C, size=(h, w)).astype(np.int64)
+            y[excl & ~q] = C
+            assert q.any() and (y == C).any() and ((q | (y == C)) == excl).all()
+            x = torch.from_numpy(gi["logits"][0])
+            with torch.no_grad():
+                pred = model(x[None])["pred"]
+                assert torch.equal(pred, x[None]), "the identity 1x1 convolution must hand the logits on bit for bit"
+                uc = refq.UncertaintySampler(st)(F.softmax(pred, dim=1))[0]
+            uc[torch.from_numpy(q)] = FILL[st]
+            uc[torch.from_numpy(y == C)] = FILL[st]
+            gaps = tc.leading_gaps_in_tol(uc.numpy(), k, largest)
+            assert gaps.min() >= tc.GUARD_TOLS, (st, i, gaps.min())
+            order = uc.flatten().topk(k, largest=largest).indices.numpy()       # query.py:57-61
+            assert order.tolist() == gi["spots"][:k].tolist()
+            xs.append(x), ys.append(torch.from_numpy(y)), prev.append(q), orders.append(order.astype(np.int32))
+            out[f"{st}_seed_{i}"] = np.int64(seed)
+            out[f"{st}_rivals_{i}"] = np.packbits(gi["rivals"])
+            out[f"{st}_spots_{i}"] = gi["spots"].astype(np.int32)
+            out[f"{st}_a_{i}"] = gi["a"]
+            out[f"{st}_prev_{i}"] = np.packbits(q.reshape(-1))
+            out[f"{st}_y_{i}"] = y.astype(np.uint8)
+            out[f"{st}_min_gap_tol_{i}"] = np.float64(gaps.min())
+        out[f"{st}_order"] = np.stack(orders)
+        ds = FakeDataset(xs, ys, prev, names)
+        with tempfile.TemporaryDirectory() as td:
+            args = mk_args(st, C, k=10, top_n_percent=0.05, dir_root=td)
+            qs = refq.QuerySelector(args, FakeLoader(ds), device=torch.device("cpu"))
+            np.random.seed(np_seed)
+            dq = qs(nth_query=1, model=model)
+            stats = pkl.load(open(f"{td}/checkpoints/golden/1_query/query_stats.pkl", "rb"))
+        for i, nme in enumerate(names):
+            xc, yc = np.asarray(dq[nme]["x_coords"], dtype=np.int64), np.asarray(dq[nme]["y_coords"], dtype=np.int64)
+            assert len(xc) == 10 and set((yc * w + xc).tolist()) <= set(orders[i].tolist())
+            out[f"{st}_x_{i}"], out[f"{st}_y_coords_{i}"] = xc, yc
+        out[f"{st}_stats_label_cnt"] = np.array([stats["label_distribution"][l] for l in range(C)], dtype=np.int64)
+        out[f"{st}_stats_avg_entropy"] = np.float64(stats["avg_entropy"])
+        out[f"{st}_stats_avg_n_unique"] = np.float64(stats["avg_n_unique_labels"])
+        out[f"{st}_stats_avg_cov"] = np.float64(stats["avg_spatial_coverage"])
+        assert ds.labelled is not None and ds.labelled[1] == 1
+    path = os.path.join(OUT, "acq_top5_default.npz")
+    np.savez_compressed(path, **out)
+    print("top5 default written", os.path.getsize(path))
+
+
 def gen_lowres():
     """SURVEY.md §8f-1 fixture: low-resolution classifier logits -> deeplab.py:55-56 F.interpolate(bilinear,
     align_corners=True) -> [:h,:w] crop (query.py:190) -> reference sampler + _select_queries."""
@@ -641,6 +713,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if "--random" in sys.argv:
         gen_random()
+        sys.exit(0)
+    if "--top5" in sys.argv:
+        gen_top5_default()
         sys.exit(0)
     if "--branches" in sys.argv:
         gen_branches()

@@ -544,6 +544,23 @@ int pp_sparse_ce_lowres_fwd_bwd(const float* low, int64_t ldx, int B, int C, int
 int pp_confusion_matrix_update(const float* logits, int B, int C, int64_t HW, int64_t sB, int64_t sC, const int64_t* target,
                                int64_t* hist, pp_stream_t stream);
 
+/* The label map and the step metrics straight from the LOW-resolution classifier output: replaces, in one launch and without
+ * materialising the full-resolution logits,
+ *   deeplab.py:55-56          pred = F.interpolate(pred, size=inputs.shape[2:], mode='bilinear', align_corners=True)
+ *   model.py:124-125,196-199  prob.argmax(dim=1) ... running_score.update(y, pred)      eval.py:60-63 the same in evaluate()
+ *   utils/metrics.py:168-177  RunningScore._fast_hist / update
+ *   low      f32 [B,h,w,ldx] channels-last classifier output, C valid channels; (H,W) the size interpolated to, (Hc,Wc) <= (H,W)
+ *            the top-left crop kept (VOC); scales and arithmetic are pp_acq_lowres_score_topk's, i.e. pp_bilinear_fwd's bits
+ *   target   [B,Hc,Wc] labels, target_kind 0 none (NULL), 1 uint8, 2 int64
+ *   pred     u8 [B,Hc,Wc] or NULL: the FIRST maximum over the classes of every interpolated pixel (C <= 256)
+ *   hist     i64 [C,C] or NULL, ACCUMULATED into: hist[t*C + argmax] += 1 where 0 <= t < C (labels >= C, 255, negative: ignored);
+ *            needs target; C <= 104 (block-private LDS counters)
+ * At least one of pred / hist.  Integer counts only: reproducible run to run.  Equal bit for bit to pp_bilinear_fwd followed by
+ * argmax / pp_confusion_matrix_update (tested). */
+int pp_predict_lowres(const float* low, int64_t ldx, int64_t B, int64_t C, int64_t h, int64_t w, int64_t H, int64_t W,
+                      int align_corners, int64_t Hc, int64_t Wc, const void* target, int target_kind, uint8_t* pred,
+                      int64_t* hist, pp_stream_t stream);
+
 /* torch.optim.Adam step on flat buffers (utils/utils.py:125-141): elements [0,n_split) use lr_a (the
  * backbone/encoder group at lr/10), the rest lr_b; L2 weight decay; `step` is 1-based; grads are
  * multiplied by grad_scale first (1/world_size after the gradient all-reduce). */

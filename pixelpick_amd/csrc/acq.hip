@@ -2357,17 +2357,6 @@ struct LowresPlan {
 constexpr size_t kLowresLdsMax = 54 * 1024;      // + 8.2 KB of static survivor lists = the 64 KB a block may ask for
 constexpr size_t kLowresLdsSoft = 32 * 1024;     // above this the 32-row tile gives way to the 16-row tile
 
-static void lowres_scales(int64_t h, int64_t w, int64_t H, int64_t W, int align, float& sh, float& sw)
-{
-    if (align) {
-        sh = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.0f;
-        sw = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.0f;
-    } else {
-        sh = (float)h / (float)H;
-        sw = (float)w / (float)W;
-    }
-}
-
 static LowresPlan make_lowres_plan(int64_t B, int64_t C, int64_t h, int64_t w, int64_t Hc, int64_t Wc, float sh, float sw,
                                    bool force_ppt4)
 {

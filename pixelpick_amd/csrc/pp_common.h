@@ -99,13 +99,26 @@ __device__ __forceinline__ Lerp lerp_src(int dst, int in, float scale, int align
     return L;
 }
 
+// the `scale` lerp_src takes, from the low-resolution size (h, w) and the size interpolated to (H, W): one statement of it for
+// every entry that interpolates from the classifier output (pp_acq_lowres_*, pp_predict_lowres)
+inline void lowres_scales(int64_t h, int64_t w, int64_t H, int64_t W, int align, float& sh, float& sw)
+{
+    if (align) {
+        sh = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.0f;
+        sw = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.0f;
+    } else {
+        sh = (float)h / (float)H;
+        sw = (float)w / (float)W;
+    }
+}
+
 // h0*(w0*v00 + w1*v01) + h1*(w0*v10 + w1*v11) with the contraction spelled out, so that every kernel that
 // interpolates (pp_bilinear_fwd and the fused low-resolution acquisition) produces the same bits.
+// (its two halves on their own, for a kernel that reuses one source-row pair for several output rows: pp_predict_lowres)
+__device__ __forceinline__ float lerp2(float l0, float l1, float v0, float v1) { return __fmaf_rn(l1, v1, __fmul_rn(l0, v0)); }
 __device__ __forceinline__ float bilerp(float h0, float h1, float w0, float w1, float v00, float v01, float v10, float v11)
 {
-    const float top = __fmaf_rn(w1, v01, __fmul_rn(w0, v00));
-    const float bot = __fmaf_rn(w1, v11, __fmul_rn(w0, v10));
-    return __fmaf_rn(h1, bot, __fmul_rn(h0, top));
+    return lerp2(h0, h1, lerp2(w0, w1, v00, v01), lerp2(w0, w1, v10, v11));
 }
 
 #ifdef __HIPCC__

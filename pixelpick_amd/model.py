@@ -12,7 +12,7 @@ Everything between the loaders is the reference's loop:
         self.dataloader.dataset.label_queries(queries, nth_query + 1)
 
 with the train step on `FlatTrainer` (HIP forward/backward, sparse CE, fused Adam, Poly lr per iteration) and the
-per-step metrics on the device (`RunningScore.update_from_logits`).  PNG dumps (`Visualiser`) are omitted.
+per-step metrics on the device (`RunningScore.update_from_lowres` / `update_from_logits`).  PNG dumps (`Visualiser`) are omitted.
 """
 import os
 from math import ceil
@@ -54,6 +54,16 @@ class Model:
         rt = getattr(args, "replay_train_step", None)
         env = os.environ.get("PIXELPICK_REPLAY_TRAIN")
         self._replay_train = (env != "0") if env is not None else (True if rt is None else bool(rt))
+        # not in the reference: the confusion matrices of the train steps and of validation are taken straight from the network's
+        # low-resolution classifier output (RunningScore.update_from_lowres, csrc/predict.hip) wherever that gives the SAME counts
+        # bit for bit as the full-resolution logits: every train step (the logits a step kept were the interpolation of that
+        # output) and the validation of models whose forward() is that interpolation (LOWRES_EXACT: DeepLab).  FPNSeg's forward()
+        # sums its branches at full resolution, so its validation only takes this path with args.metrics_from_lowres = True.
+        # args.metrics_from_lowres = False or PIXELPICK_METRICS_LOWRES=0 restore the full-resolution calls everywhere.
+        ml = getattr(args, "metrics_from_lowres", None)
+        env = os.environ.get("PIXELPICK_METRICS_LOWRES")
+        self._metrics_lowres = (env != "0") if env is not None else (True if ml is None else bool(ml))
+        self._metrics_lowres_forced = self._metrics_lowres and ml is True
         self.device = device or torch.device("cuda:0")
         self.dir_checkpoints = f"{args.dir_root}/checkpoints/{args.experim_name}"
         self.experim_name = args.experim_name
@@ -179,6 +189,9 @@ class Model:
         n_batches = len(self.dataloader)
         n_local = n_batches // self.world if n_batches >= self.world else 0      # equal step counts on every rank
         local_it = -1
+        from . import trainer as _tr
+        keep = "low" if (self._metrics_lowres and _tr.SPARSE_LOWRES_CE and getattr(model, "LOWRES_LOGITS", False)
+                         and self.n_classes <= 104) else True
         for it, dict_data in enumerate(loader):
             if skip:
                 if it >= n_local * self.world:
@@ -223,12 +236,15 @@ class Model:
                 # first step runs eagerly: it is the one in which the layers that keep per-step state register themselves - the
                 # bf16x3 weight planes split at begin_step, engine._X3_WPL - so that the recorded step contains that work.)
                 trainer._ensure_train_mode()
-                trainer.enable_replay(x, y, warmup=0)
+                trainer.enable_replay(x, y, warmup=0, keep_logits=keep)
             else:
                 if trainer._plan is not None and tuple(x.shape) != tuple(trainer._gx.shape):
                     trainer.disable_replay()                                # a ragged batch: back to eager steps
-                trainer.train_step(x, y, keep_logits=True)
-            self.running_score.update_from_logits(y, trainer.last_logits)  # device-side confusion matrix (L6)
+                trainer.train_step(x, y, keep_logits=keep)
+            if trainer.last_low is not None:                               # device-side confusion matrix (L6), from the classifier output
+                self.running_score.update_from_lowres(y, trainer.last_low, trainer.last_low_size, align_corners=trainer.last_low_align)
+            else:
+                self.running_score.update_from_logits(y, trainer.last_logits)
             self.running_loss.update(trainer.last_loss)
             if self.debug:
                 break
@@ -296,20 +312,28 @@ class Model:
         # launches), so consecutive images of equal size are forwarded `val_batch_size` at a time (default 8).
         vbs = int(getattr(self.args, "val_batch_size", 8))
         pend_x, pend_y = [], []
+        lowres = (self._metrics_lowres and callable(getattr(model, "forward_lowres", None)) and self.n_classes <= 104
+                  and (getattr(model, "LOWRES_EXACT", False) or self._metrics_lowres_forced))
 
         def flush():
             if not pend_x:
                 return
             xs, ys = torch.cat(pend_x, dim=0), torch.cat(pend_y, dim=0)
+            crop = None
             if self.dataset_name == "voc":
                 h, w = ys.shape[1:]
                 pad_h = ceil(h / self.stride_total) * self.stride_total - xs.shape[2]
                 pad_w = ceil(w / self.stride_total) * self.stride_total - xs.shape[3]
                 xs = F.pad(xs, pad=(0, pad_w, 0, pad_h), mode='reflect')
-                logits = model(xs)['pred'][:, :, :h, :w].contiguous()
+                crop = (h, w)
+            if lowres:
+                low, size = model.forward_lowres(xs)
+                self.running_score.update_from_lowres(ys, low, size, crop=crop, align_corners=model.LOWRES_ALIGN_CORNERS)
             else:
                 logits = model(xs)['pred']
-            self.running_score.update_from_logits(ys, logits)
+                if crop is not None:
+                    logits = logits[:, :, :crop[0], :crop[1]].contiguous()
+                self.running_score.update_from_logits(ys, logits)
             pend_x.clear()
             pend_y.clear()
 

@@ -71,6 +71,7 @@ class DeepLab(nn.Module):
     the imported reference parts (tools/gen_golden_net.py --r50)."""
     LOWRES_LOGITS = True      # _run(..., upsample=False) stops in front of the final x4 bilinear (deeplab.py:55-56)
     LOWRES_ALIGN_CORNERS = True
+    LOWRES_EXACT = True       # forward()['pred'] IS bilinear(forward_lowres()): metrics taken from the classifier output are the same bits
 
     def __init__(self, args, backbone='mobilenet', output_stride=16):
         super().__init__()
@@ -142,6 +143,14 @@ class DeepLab(nn.Module):
             raise RuntimeError("pixelpick_amd.DeepLab runs on the GPU only (no CPU fallback)")
         pred_v, _ = self._run(E.Tape(enabled=False), inputs.to(torch.float32), upsample=False)
         return pred_v.t, tuple(inputs.shape[2:])
+
+    @torch.no_grad()
+    def predict(self, inputs):
+        """The label map forward(inputs)['pred'].argmax(dim=1) (model.py:124,197, eval.py:61) as uint8 [B,H,W], taken from the
+        classifier output in one launch (pp_predict_lowres): the full-resolution logits are never written."""
+        from ..predict import predict_lowres
+        low, size = self.forward_lowres(inputs)
+        return predict_lowres(low, size, align_corners=self.LOWRES_ALIGN_CORNERS)[0]
 
     def forward(self, inputs):
         if not inputs.is_cuda:

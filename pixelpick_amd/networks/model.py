@@ -86,6 +86,15 @@ class FPNSeg(nn.Module):
         low = pred_v.t
         return low, (2 * low.shape[1], 2 * low.shape[2])
 
+    @torch.no_grad()
+    def predict(self, inputs):
+        """The label map as uint8 [B,H,W]: argmax over the classes of the interpolated classifier output (forward_lowres +
+        pp_predict_lowres).  forward() sums the branches at full resolution, which is the same map in exact arithmetic; in
+        fp32 the two can differ where the top two logits are within rounding of each other."""
+        from ..predict import predict_lowres
+        low, size = self.forward_lowres(inputs)
+        return predict_lowres(low, size, align_corners=self.LOWRES_ALIGN_CORNERS)[0]
+
     def forward(self, x):
         if not x.is_cuda:
             raise RuntimeError("pixelpick_amd.FPNSeg runs on the GPU only (no CPU fallback)")

@@ -139,6 +139,9 @@ class FlatTrainer:
         self.lr_factor = 1.0
         self.last_loss: Optional[torch.Tensor] = None
         self.last_logits: Optional[torch.Tensor] = None
+        self.last_low: Optional[torch.Tensor] = None       # keep_logits="low": the classifier output, its target size and
+        self.last_low_size = None                          # align_corners flag
+        self.last_low_align = True
         # run-time hyper-parameters live in device memory so that the whole step can be replayed from a recorded launch list:
         # hyper = [lr_backbone, lr_head, 1-beta1^t, sqrt(1-beta2^t)], seed = per-step dropout base seed
         # (a ring of pinned staging slots: the host runs ahead of graph replays, so a slot is only rewritten once the copy
@@ -162,8 +165,10 @@ class FlatTrainer:
                 self.model.train()
                 return
 
-    def forward_backward(self, x: torch.Tensor, y: torch.Tensor, keep_logits: bool = False) -> torch.Tensor:
-        """x [B,3,H,W] f32, y [B,H,W] int64 with ignore_index at unlabelled pixels (model.py:108-110)."""
+    def forward_backward(self, x: torch.Tensor, y: torch.Tensor, keep_logits=False) -> torch.Tensor:
+        """x [B,3,H,W] f32, y [B,H,W] int64 with ignore_index at unlabelled pixels (model.py:108-110).
+        keep_logits: False; True -> last_logits = the [B,C,H,W] logits; "low" -> last_low = the classifier output [B,h,w,C]
+        with last_low_size / last_low_align (what F.interpolate would be called with), last_logits stays None."""
         tape = E.Tape(enabled=True)
         tape.param_grad_dst = lambda p: self._grad_view.get(id(p))
         self._early_work = None
@@ -179,12 +184,23 @@ class FlatTrainer:
             size = tuple(x.shape[2:])
             align = bool(getattr(self.model, "LOWRES_ALIGN_CORNERS", True))     # DeepLab: align_corners=True x4; FPNSeg: False, x2
             loss, dlow = E.cross_entropy_lowres(low.t, size, y, self.ignore_index, align_corners=align, sparse=self.sparse_labels)
-            self.last_logits = (E.bilinear(E.Tape(False), low, size, align, 0.0 if align else float(getattr(self.model, "LOWRES_SCALE_FACTOR", 0.0)),
-                                           out_nchw=True).t if keep_logits else None)
+            if keep_logits == "low":
+                # the step metrics interpolate the classifier output themselves (RunningScore.update_from_lowres): no
+                # full-resolution E.bilinear in this mode
+                self.last_logits = None
+                self.last_low, self.last_low_size, self.last_low_align = low.t, size, align
+            else:
+                self.last_low = None
+                self.last_logits = (E.bilinear(E.Tape(False), low, size, align, 0.0 if align else float(getattr(self.model, "LOWRES_SCALE_FACTOR", 0.0)),
+                                               out_nchw=True).t if keep_logits else None)
             tape.backward(low, dlow)
         else:
+            if keep_logits == "low":
+                raise ValueError('keep_logits="low" needs a model whose logits are interpolated from its classifier output '
+                                 '(LOWRES_LOGITS) and the low-resolution loss path')
             pred, _ = self.model._run(tape, x)
             loss, dlogits = E.cross_entropy_nchw(pred.t, y, self.ignore_index, sparse=self.sparse_labels)
+            self.last_low = None
             self.last_logits = pred.t if keep_logits else None
             tape.backward(pred, dlogits)
         self.last_loss = loss
@@ -307,7 +323,7 @@ class FlatTrainer:
         E.end_step()
         return loss
 
-    def train_step(self, x: torch.Tensor, y: torch.Tensor, keep_logits: bool = False) -> torch.Tensor:
+    def train_step(self, x: torch.Tensor, y: torch.Tensor, keep_logits=False) -> torch.Tensor:
         """One optimisation step (model.py:101-122).  After enable_replay() the recorded launch list is re-issued."""
         self._ensure_train_mode()
         self.step_count += 1
@@ -325,7 +341,7 @@ class FlatTrainer:
             return self.last_loss
         return self._step_body(x, y, keep_logits, False)
 
-    def enable_replay(self, x: torch.Tensor, y: torch.Tensor, warmup: int = 1):
+    def enable_replay(self, x: torch.Tensor, y: torch.Tensor, warmup: int = 1, keep_logits=True):
         """Record the launches of one step for this input shape (~415 C-ABI calls, ~110 stream fork / join operations, the
         all-reduces at N > 1) as a _lib.LaunchPlan and re-issue them from a tight loop in every later train_step(): the
         Python around each launch (5.4 ms per 6.85 ms step) is paid once.  The GPU schedule is the eager one - main stream,
@@ -334,7 +350,9 @@ class FlatTrainer:
         The step runs on private copies of x / y, per-step scalars
         (learning rates, Adam bias corrections, dropout seed) are read from device memory, and the recorded step allocates
         from a private memory pool that is kept, so every address in the plan stays valid and is never handed to another
-        tensor.  `warmup` eager steps (real optimisation steps, as is the recorded one) first grow the scratch buffers."""
+        tensor.  `warmup` eager steps (real optimisation steps, as is the recorded one) first grow the scratch buffers.
+        `keep_logits` is what the recorded step keeps (forward_backward): True (default) the full-resolution logits, "low" the
+        classifier output only, False neither."""
         assert self._plan is None
         self.model.train()
         E.set_dropout_device_seed(self._seed_dev)
@@ -344,13 +362,13 @@ class FlatTrainer:
         for _ in range(warmup):
             self.step_count += 1
             self._stage_hyper()
-            self._step_body(self._gx, self._gy, True, True)
+            self._step_body(self._gx, self._gy, keep_logits, True)
         self.step_count += 1
         self._stage_hyper()
         pool = torch.cuda.MemPool()
         with torch.cuda.use_mem_pool(pool, device=x.device):
             with _lib.record_plan(native=NATIVE_PLAN) as plan:
-                self._step_body(self._gx, self._gy, True, True)
+                self._step_body(self._gx, self._gy, keep_logits, True)
         self._plan, self._plan_pool = plan, pool
         self._plan_stream = torch.cuda.current_stream(x.device).cuda_stream
         return self
@@ -377,7 +395,7 @@ class FlatTrainer:
         """Back to eager steps; also removes the process-wide device seed word enable_replay() installed, so that later
         eager trainers / MC-dropout forwards draw their masks from the host counter again."""
         if self._plan is not None:
-            self.last_loss = self.last_logits = None      # they live in the plan's memory pool
+            self.last_loss = self.last_logits = self.last_low = None      # they live in the plan's memory pool
             # the plan holds bound methods of this trainer (all_reduce_grads, _early_all_reduce_on): clear it so that no
             # trainer <-> plan reference cycle keeps the memory pool (a full step of activations) alive until a GC pass
             if hasattr(self._plan, "close"):

@@ -2,7 +2,9 @@
 
 RunningScore keeps the reference's numpy `update(label_trues, label_preds)` for host arrays and adds
 `update_from_logits(y, logits)`: argmax + confusion-matrix histogram on the device (pp_confusion_matrix_update),
-so a train/val step ships C*C int64 to the host instead of two full-resolution maps (model.py:124-125)."""
+so a train/val step ships C*C int64 to the host instead of two full-resolution maps (model.py:124-125), and
+`update_from_lowres(y, low, size)`: the same histogram taken straight from the low-resolution classifier output
+(pp_predict_lowres), for networks whose logits are a bilinear interpolation of it."""
 import numpy as np
 import torch
 
@@ -60,6 +62,22 @@ class RunningScore(object):
         rc = _lib.lib().pp_confusion_matrix_update(logits.data_ptr(), B, C, H * W, logits.stride(0), logits.stride(1), y.data_ptr(),
                                                    self._dev_hist.data_ptr(), _lib.current_stream_ptr(logits.device))
         _lib.check(rc, "pp_confusion_matrix_update")
+
+    def update_from_lowres(self, y: torch.Tensor, low: torch.Tensor, size, crop=None, align_corners: bool = True):
+        """update_from_logits(y, F.interpolate(low, size, 'bilinear', align_corners)[:, :, :crop_h, :crop_w]) - the same counts,
+        bit for bit - in one launch that never writes the full-resolution logits (pp_predict_lowres).  low [B,h,w,C] f32
+        channels-last classifier output on the GPU; y [B,crop_h,crop_w] int64 or uint8; accumulates on the device, no sync."""
+        from ..predict import predict_lowres
+        if low.dim() != 4 or low.shape[3] != self.n_classes:
+            raise ValueError(f"low must be [B,h,w,{self.n_classes}] channels-last, got {tuple(low.shape)}")
+        y = torch.as_tensor(y)
+        if y.dtype not in (torch.uint8, torch.int64):
+            y = y.to(torch.int64)
+        y = y.to(low.device).contiguous()
+        if self._dev_hist is None:
+            self._dev_hist = torch.zeros((self.n_classes, self.n_classes), dtype=torch.int64, device=low.device)
+        predict_lowres(low, size, crop=crop, align_corners=align_corners, target=y, hist=self._dev_hist, want_pred=False)
+        return self
 
     def _sync(self):
         if self._dev_hist is not None:

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Training-loop throughput THROUGH the active-learning driver (pixelpick_amd/model.py:_train_epoch: dataloader ->
-H2D -> label sparsification -> train step -> device-side confusion matrix -> running loss) vs the bare train step."""
+H2D -> label sparsification -> train step -> device-side confusion matrix -> running loss) and through its validation
+loop (_val), with the dataloader's own cost beside them.  PIXELPICK_METRICS_LOWRES=0 takes the metrics from full-resolution logits."""
 import os, sys, time, warnings, io, contextlib, tempfile
 from argparse import Namespace
 import numpy as np
@@ -35,6 +36,19 @@ with tempfile.TemporaryDirectory() as td:
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
     print(f"driver train loop: {2 * (N // 4) * 4 / dt:7.1f} images/s ({dt / (2 * (N // 4)) * 1e3:.2f} ms/step)")
+    # the validation loop (model.py:_val: loader -> H2D -> eval forward, val_batch_size images at a time -> device-side confusion matrix)
+    NV = int(os.environ.get("N_VAL", 64))
+    m.dataloader_val = mk(SyntheticDataset(NV, H, W, C, C, seed=3), 1, False)
+    os.makedirs(f"{m.dir_checkpoints}/{m.nth_query}_query", exist_ok=True)
+    with contextlib.redirect_stdout(io.StringIO()):
+        m._val(1, model)                            # warm-up pass (also writes the best-mIoU checkpoint once)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for e in range(2, 4):
+            m._val(e, model)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+    print(f"driver val loop  : {2 * NV / dt:7.1f} images/s ({dt / (2 * NV) * 1e3:.2f} ms/image)")
     t0 = time.perf_counter()
     for _ in mk(ds, 4, True):
         pass

@@ -84,10 +84,25 @@ def load_pair(dataset: str, p_img: str, p_lab: str):
     return torch.from_numpy(xa).permute(2, 0, 1).contiguous(), torch.from_numpy(ya.astype(np.int64))
 
 
+class ValSet:
+    """The validation split with the surface pixelpick_amd.eval.evaluate() reads from `dataloader.dataset`."""
+
+    def __init__(self, dataset: str, root: str, n_classes: int):
+        self.dataset_name = {"cs": "cs", "cv": "cv", "voc": "voc"}[dataset]
+        self.n_classes = n_classes
+        self._kind, self._items = dataset, val_items(dataset, root)
+
+    def __len__(self):
+        return len(self._items)
+
+    def __getitem__(self, i):
+        x, y = load_pair(self._kind, *self._items[i])
+        return {"x": x, "y": y}
+
+
 def evaluate(key: str, ckpt: str, root: str) -> float:
     import torch
-    import torch.nn.functional as F
-    from pixelpick_amd.utils.metrics import RunningScore
+    from pixelpick_amd import eval as pp_eval
     from pixelpick_amd.utils.utils import get_model
     _, dataset, net, C, _ignore, _ = MODELS[key]
     args = Namespace(use_mc_dropout=False, mc_dropout_p=0.2, n_classes=C, network_name=net, weight_type="random", n_layers=50,
@@ -97,18 +112,10 @@ def evaluate(key: str, ckpt: str, root: str) -> float:
     sd = torch.load(ckpt, map_location="cpu")
     model.load_state_dict(sd["model"] if "model" in sd else sd)    # model.py:208-213 writes {"model": state_dict}
     model = model.cuda().eval()
-    score = RunningScore(C)
-    with torch.no_grad():
-        for p_img, p_lab in val_items(dataset, root):
-            x, y = load_pair(dataset, p_img, p_lab)
-            h, w = y.shape
-            ph, pw = (-h) % 32, (-w) % 32                          # VOC: reflect-pad to the stride, crop back (model.py:181-189, query.py:174)
-            xb = x[None].cuda()
-            if ph or pw:
-                xb = F.pad(xb, (0, pw, 0, ph), mode="reflect")
-            pred = model(xb)["pred"][:, :, :h, :w]
-            score.update_from_logits(y[None].cuda(), pred.contiguous())      # labels outside [0, C) - the void id - are not counted (utils/metrics.py:168-177)
-    return 100.0 * float(score.get_scores()[0]["Mean IoU"])
+    # eval.py:15-94 on the HIP path: VOC is reflect-padded to the stride and cropped back (model.py:181-189, query.py:174); labels
+    # outside [0, C) - the void id - are not counted (utils/metrics.py:168-177); the full-resolution logits are never written
+    loader = torch.utils.data.DataLoader(ValSet(dataset, root, C), batch_size=1, shuffle=False)
+    return 100.0 * float(pp_eval.evaluate(model, loader, key, stride_total=32, device=torch.device("cuda:0")))
 
 
 def main():

@@ -135,6 +135,32 @@ int pp_acq_lowres_score_at(const float* low, int64_t ldx, int64_t B, int64_t C, 
                            const int32_t* img_idx, const int32_t* pix_idx, int64_t n, float* out,
                            pp_stream_t stream);
 
+/* MC-dropout acquisition straight from the low-resolution classifier output: the mean over T stochastic passes of the
+ * strategy's score, then exclusion and top-k, in one launch and without the T full-resolution logit tensors.  Replaces
+ *   deeplab.py:55-56   the x4 (x2) bilinear upsample of every pass
+ *   query.py:177-187   uc_map += uncertainty_sampler(softmax(model(x)["pred"][:, :, :h, :w])) per pass, / mc_n_steps
+ *   query.py:190, 195-201, 57-61   softmax, exclusion fill, top-k   (as pp_acq_lowres_score_topk)
+ *   low      f32 [B*T,h,w,ldx] channels-last, IMAGE-MAJOR: passes t = 0..T-1 of image b are entries b*T + t
+ *   scale    the factor on the sum over the passes (1 / mc_n_steps)
+ * Everything else - H, W, align_corners, the crop Hc x Wc, exclude, k == 0 (map only), the ordering policy, the error codes and
+ * the workspace, pp_acq_lowres_workspace_bytes(B, C, Hc, Wc, k) (T does not enter) - is pp_acq_lowres_score_topk's.
+ * C <= 64 (PP_ACQ_MAX_CLASSES); wider heads return PP_ERR_UNSUPPORTED (pp_bilinear_fwd + pp_acq_softmax_sum serve them).
+ * The result equals pp_bilinear_fwd of the B*T entries, pp_acq_softmax_sum(accumulate = 0) per image, the fill at excluded
+ * pixels and pp_topk_select, bit for bit (tested): per-pass scores in the reference's operation order, NaN (0 * log 0,
+ * query.py:230) in any pass makes the mean NaN. */
+int pp_acq_lowres_mc_score_topk(const float* low, int64_t ldx, int64_t B, int64_t T, int64_t C, int64_t h, int64_t w,
+                                int64_t H, int64_t W, int align_corners, int64_t Hc, int64_t Wc,
+                                const uint8_t* exclude, int strategy, float scale, int64_t k,
+                                int32_t* out_idx, float* out_val, float* out_map,
+                                void* workspace, size_t ws_bytes, pp_stream_t stream);
+
+/* The strategy's score OF THE MEAN PROBABILITY p_c = scale * sum_t softmax(x_t)_c (no exclusion) at n listed pixels, as
+ * pp_acq_lowres_score_at lists them: QueryStats._get_entropy(query, prob) of the MC-dropout branch (query.py:262-264 on the
+ * `prob` of :177-187) at the picked pixels only - no [C,H,W] mean-probability map.  Formulas: pp_uncertainty_from_prob's. */
+int pp_acq_lowres_mc_score_at(const float* low, int64_t ldx, int64_t B, int64_t T, int64_t C, int64_t h, int64_t w,
+                              int64_t H, int64_t W, int align_corners, int64_t Hc, int64_t Wc, int strategy, float scale,
+                              const int32_t* img_idx, const int32_t* pix_idx, int64_t n, float* out, pp_stream_t stream);
+
 
 /* =============================================================================================
  * Network layers (DeepLabv3+-MobileNetV2 / FPN-ResNet50 forward + backward), NHWC fp32.

@@ -213,3 +213,66 @@ def score_at_lowres(low: torch.Tensor, size, img_idx, pix_idx, strategy: str = "
                                                _lib.current_stream_ptr(dev))
     _lib.check(rc, "pp_acq_lowres_score_at")
     return out
+
+
+# ---- MC-dropout from the low-resolution classifier output (query.py:177-187) -------------------------------------
+MC_LOWRES_MAX_CLASSES = 64     # PP_ACQ_MAX_CLASSES (include/pixelpick_hip.h): wider heads are PP_ERR_UNSUPPORTED there
+
+
+def _mc_geom(low: torch.Tensor, n_passes: int, size, crop):
+    T = int(n_passes)
+    if isinstance(low, torch.Tensor) and low.ndim == 4 and (T < 1 or low.shape[0] % T != 0):
+        raise ValueError(f"low holds {low.shape[0]} entries: not a multiple of n_passes = {n_passes}")
+    BT, h, w, C, ldx, H, W, Hc, Wc = _lowres_geom(low, size, crop)
+    return BT // T, T, h, w, C, ldx, H, W, Hc, Wc
+
+
+def mc_score_topk_lowres(low: torch.Tensor, n_passes: int, size, exclude, strategy: str, k: int, crop=None,
+                         align_corners: bool = True, return_map: bool = False
+                         ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """score_topk_lowres on the MEAN over n_passes stochastic passes of the strategy's score (query.py:177-187): one launch, no
+    full-resolution logits of any pass.
+
+    low [B*n_passes,h,w,C] f32 channels-last on the GPU, image-major (the passes of image b are entries b*n_passes ..
+    (b+1)*n_passes - 1).  exclude [B,crop_h,crop_w].  Returns (idx int32 [B,k], val f32 [B,k], map f32 [B,crop_h,crop_w] | None);
+    k == 0 -> (None, None, map)."""
+    B, T, h, w, C, ldx, H, W, Hc, Wc = _mc_geom(low, n_passes, size, crop)
+    L = _lib.lib()
+    dev = low.device
+    ex = _exclude_u8(exclude, B, Hc, Wc, dev)
+    want_map = return_map or k == 0
+    idx = torch.empty((B, k), dtype=torch.int32, device=dev) if k else None
+    val = torch.empty((B, k), dtype=torch.float32, device=dev) if k else None
+    omap = torch.empty((B, Hc, Wc), dtype=torch.float32, device=dev) if want_map else None
+    ws = _ws(L.pp_acq_lowres_workspace_bytes(B, C, Hc, Wc, k), dev) if k else None
+    with torch.cuda.device(dev):
+        rc = L.pp_acq_lowres_mc_score_topk(low.data_ptr(), ldx, B, T, C, h, w, H, W, int(bool(align_corners)), Hc, Wc,
+                                           ex.data_ptr() if ex is not None else None, strategy_id(strategy), 1.0 / T, k,
+                                           idx.data_ptr() if k else None, val.data_ptr() if k else None,
+                                           omap.data_ptr() if omap is not None else None,
+                                           ws.data_ptr() if k else None, ws.numel() if k else 0, _lib.current_stream_ptr(dev))
+    _lib.check(rc, "pp_acq_lowres_mc_score_topk")
+    return idx, val, omap
+
+
+def mc_score_at_lowres(low: torch.Tensor, n_passes: int, size, img_idx, pix_idx, strategy: str = "entropy", crop=None,
+                       align_corners: bool = True) -> torch.Tensor:
+    """The strategy's score of the MEAN PROBABILITY over the n_passes passes (no exclusion) at listed pixels: pixel i = image
+    img_idx[i], flat index pix_idx[i] = y*crop_w + x.  -> f32 [n] on the GPU.  (QueryStats._get_entropy(query, prob) of the
+    MC-dropout branch, query.py:262-264, at the queried pixels only.)"""
+    B, T, h, w, C, ldx, H, W, Hc, Wc = _mc_geom(low, n_passes, size, crop)
+    dev = low.device
+    ii = torch.as_tensor(img_idx).to(torch.int32).to(dev).contiguous()
+    pp = torch.as_tensor(pix_idx).to(torch.int32).to(dev).contiguous()
+    if ii.shape != pp.shape or ii.ndim != 1:
+        raise ValueError("img_idx and pix_idx must be 1-d and of equal length")
+    n = ii.numel()
+    out = torch.empty((n,), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    with torch.cuda.device(dev):
+        rc = _lib.lib().pp_acq_lowres_mc_score_at(low.data_ptr(), ldx, B, T, C, h, w, H, W, int(bool(align_corners)), Hc, Wc,
+                                                  strategy_id(strategy), 1.0 / T, ii.data_ptr(), pp.data_ptr(), n, out.data_ptr(),
+                                                  _lib.current_stream_ptr(dev))
+    _lib.check(rc, "pp_acq_lowres_mc_score_at")
+    return out

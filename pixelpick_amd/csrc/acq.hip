@@ -181,6 +181,60 @@ __device__ __forceinline__ float pixel_score_fast(const float (&x)[CMAX], int C,
     }
 }
 
+// ---- MC-dropout: the score of ONE stochastic pass at one pixel (query.py:181-187) ---------------------------------
+// softmax_sum_kernel's arithmetic, shared with the low-resolution MC scorers so that both produce the same bits:
+//   m = max_c x_c ; S = sum_c expf(x_c - m) ; p_c = expf(x_c - m) / S ; then the strategy's formula on p in class order
+// (libm expf / logf, the reference's operation order; the entropy term is ONE fused multiply-add per class, spelled out so that
+// it does not depend on how a caller's loop was unrolled).  x(c): the pass's logit of class c; on_prob(c, p_c): called once per class.
+//   CMAX == 0  any class count: the loops run to C and expf is evaluated twice per class (softmax_sum_kernel)
+//   CMAX  > 0  C <= CMAX (EXACT: C == CMAX), loops unrolled, expf(x_c - m) stays in registers between the sum and the division
+//   STRAT >= 0 the strategy is a compile-time constant: only its own chain is computed (no logf outside entropy)
+template <int STRAT, int CMAX, bool EXACT, typename X, typename P>
+__device__ __forceinline__ float mc_pass_score(X x, int C, int strategy_rt, P on_prob)
+{
+    constexpr bool kReg = CMAX > 0;
+    constexpr bool kEnt = STRAT < 0 || STRAT == PP_ACQ_ENTROPY, kT1 = STRAT < 0 || STRAT != PP_ACQ_ENTROPY,
+                   kT2 = STRAT < 0 || STRAT == PP_ACQ_MARGIN;
+    const int strategy = STRAT >= 0 ? STRAT : strategy_rt;
+    const int n = kReg ? CMAX : C;
+    float e[kReg ? CMAX : 1];
+    float m = x(0);
+    if constexpr (kReg) {
+#pragma unroll
+        for (int c = 1; c < CMAX; ++c)
+            if (EXACT || c < C) m = fmaxf(m, x(c));
+    } else {
+        for (int c = 1; c < n; ++c) m = fmaxf(m, x(c));
+    }
+    float S = 0.0f;
+    if constexpr (kReg) {
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c)
+            if (EXACT || c < C) {
+                e[c] = expf(x(c) - m);
+                S += e[c];
+            }
+    } else {
+        for (int c = 0; c < n; ++c) S += expf(x(c) - m);
+    }
+    float ent = 0.0f, t1 = -INFINITY, t2 = -INFINITY;
+    auto one = [&](int c, float ec) {
+        const float pc = ec / S;
+        on_prob(c, pc);
+        if (kEnt) ent = fmaf(-pc, logf(pc), ent);
+        if (kT2) t2 = fmaxf(t2, fminf(t1, pc));
+        if (kT1) t1 = fmaxf(t1, pc);
+    };
+    if constexpr (kReg) {
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c)
+            if (EXACT || c < C) one(c, e[c]);
+    } else {
+        for (int c = 0; c < n; ++c) one(c, expf(x(c) - m));
+    }
+    return strategy == PP_ACQ_ENTROPY ? ent : (strategy == PP_ACQ_LEAST_CONFIDENCE ? 1.0f - t1 : fabsf(t1 - t2));
+}
+
 // ---- per-wave top-k extraction -------------------------------------------------------------------
 // Each lane holds PPT (key, ~idx) pairs; k rounds of {lane-local max, two DPP wave reductions,
 // knock out the winner}.  Winner order == global order (key desc, index asc).  Lane 0 stores.
@@ -734,6 +788,158 @@ __global__ __launch_bounds__(kBlock) void acq_lowres_at_kernel(const float* low,
     for (int c = 0; c < CMAX; ++c)
         if (EXACT || c < C) x[c] = bilerp(lh.l0, lh.l1, lw.l0, lw.l1, p00[c], p01[c], p10[c], p11[c]);
     out[i] = pixel_score_fast<CMAX, EXACT>(x, C, strategy);
+}
+
+// ---- MC-dropout acquisition from the low-resolution classifier output (query.py:177-187) --------------------------------
+// The mean over T stochastic passes of the strategy's score, without the T full-resolution logit tensors (T x 10 MB per 256x512x19
+// image written by pp_bilinear_fwd and read back by softmax_sum_kernel): acq_lowres_kernel's tile, looped over the passes.  `low`
+// is image-major, passes t = 0..T-1 of image b are entries b*T + t.  Per pass the block stages that pass's source patch in LDS
+// (same geometry and odd pixel pitch), every lane interpolates its pixels' class vectors with bilerp() and adds mc_pass_score()
+// - softmax_sum_kernel's arithmetic - to a per-pixel register accumulator; scale * sum, the exclusion fill and the selection
+// epilogues of acq_lowres_kernel follow.  The HOST guarantees that the patch fits p.patch_cap (make_lowres_plan's bound on the
+// patch of any tile); a shape whose patch does not fit runs the LDS = false form, which reads the four neighbours from memory.
+struct LowresMcParams {
+    LowresParams g;      // low: [B*T,h,w,ldx]
+    int T;
+    float scale;
+};
+
+template <int CMAX, bool EXACT, int PPT, bool LDS, int STRAT>
+__global__ __launch_bounds__(kBlock, 2) void acq_lowres_mc_kernel(LowresMcParams q)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_patch[];
+    __shared__ uint64_t s_surv[kBlock / kWave][kSurvCap];
+    __shared__ uint32_t s_cnt[kBlock / kWave];
+    __shared__ uint64_t s_top[(kBlock / kWave) * kSmallKMax];
+    const LowresParams& p = q.g;
+    constexpr int TR = (kBlock / kWave) * PPT, TC = kWave;
+    const int tiles = p.tiles_x * p.tiles_y;
+    const int img = blockIdx.x / tiles;
+    const int t = blockIdx.x - img * tiles;
+    const int ty = t / p.tiles_x, tx = t - ty * p.tiles_x;
+    const int tid = threadIdx.x, lane = tid & (kWave - 1);
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    uint32_t* qbins = reinterpret_cast<uint32_t*>(&s_surv[0][0]);
+    const bool hist = p.qhist != nullptr;
+    if (hist) {
+        for (int i = tid; i < kQBins; i += kBlock) qbins[i] = 0u;
+        __syncthreads();
+    }
+    const int C = EXACT ? CMAX : p.C;
+    const int CP = C | 1;
+    const bool largest = p.strategy != PP_ACQ_MARGIN;
+    const float fill = largest ? 0.0f : 1.0f;
+    const int64_t N = (int64_t)p.Hc * p.Wc;
+    const int X0 = tx * TC, Y0 = ty * TR;
+    const int X1 = min(X0 + TC - 1, p.Wc - 1), Y1 = min(Y0 + TR - 1, p.Hc - 1);
+    const int c_lo = lerp_src(X0, p.w, p.sw, p.align).i0, c_hi = lerp_src(X1, p.w, p.sw, p.align).i1;
+    const int r_lo = lerp_src(Y0, p.h, p.sh, p.align).i0, r_hi = lerp_src(Y1, p.h, p.sh, p.align).i1;
+    const int pw = c_hi - c_lo + 1, ph = r_hi - r_lo + 1;
+    const int64_t pass_stride = (int64_t)p.h * p.w * p.ldx;
+    const float* img_base = p.low + (int64_t)img * q.T * pass_stride;
+    const int X = X0 + lane;
+    const bool xin = X < p.Wc;
+    const Lerp lw = lerp_src(xin ? X : X1, p.w, p.sw, p.align);
+    const int64_t pitch = LDS ? (int64_t)CP : p.ldx;
+    const int64_t o0 = (int64_t)(LDS ? lw.i0 - c_lo : lw.i0) * pitch, o1 = (int64_t)(LDS ? lw.i1 - c_lo : lw.i1) * pitch;
+    const int64_t row_pitch = (LDS ? pw : p.w) * pitch;
+
+    float uc[PPT];
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) uc[j] = 0.0f;
+    for (int ps = 0; ps < q.T; ++ps) {
+        const float* base = img_base + (int64_t)ps * pass_stride;
+        if constexpr (LDS) {
+            if (ps) __syncthreads();          // every wave has finished reading the previous pass's patch
+            const int n = ph * pw * C;
+            for (int e = tid; e < n; e += kBlock) {
+                const int pc = e / C, ch = e - pc * C;
+                const int r = pc / pw, c = pc - r * pw;
+                s_patch[pc * CP + ch] = base[((int64_t)(r_lo + r) * p.w + c_lo + c) * p.ldx + ch];
+            }
+            __syncthreads();
+        }
+        const float* src = LDS ? s_patch : base;
+#pragma unroll
+        for (int j = 0; j < PPT; ++j) {
+            const int Y = Y0 + wv * PPT + j;
+            if (Y < p.Hc && xin) {
+                const Lerp lh = lerp_src(Y, p.h, p.sh, p.align);
+                const float* r0 = src + (int64_t)(LDS ? lh.i0 - r_lo : lh.i0) * row_pitch;
+                const float* r1 = src + (int64_t)(LDS ? lh.i1 - r_lo : lh.i1) * row_pitch;
+                float x[CMAX];
+#pragma unroll
+                for (int c = 0; c < CMAX; ++c)
+                    if (EXACT || c < C)
+                        x[c] = bilerp(lh.l0, lh.l1, lw.l0, lw.l1, r0[o0 + c], r0[o1 + c], r1[o0 + c], r1[o1 + c]);
+                uc[j] += mc_pass_score<STRAT, CMAX, EXACT>([&](int c) { return x[c]; }, C, p.strategy, [](int, float) {});
+            }
+            __builtin_amdgcn_sched_barrier(0);   // one pixel's class vector live at a time
+        }
+    }
+
+    const uint8_t* excl = p.exclude ? p.exclude + (int64_t)img * N : nullptr;
+    float* omap = p.out_map ? p.out_map + (int64_t)img * N : nullptr;
+    uint32_t kh[PPT], kl[PPT];
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) {
+        const int Y = Y0 + wv * PPT + j;
+        if (Y < p.Hc && xin) {
+            float sc = q.scale * uc[j];
+            const int64_t pix = (int64_t)Y * p.Wc + X;
+            if (excl && excl[pix]) sc = fill;
+            if (omap) omap[pix] = sc;
+            if (hist) atomicAdd(&qbins[qbin(sc, largest, p.qscale)], 1u);
+            kh[j] = order_key(sc, largest);
+            kl[j] = 0xFFFFFFFFu - (uint32_t)pix;
+        } else {
+            kh[j] = 0u; kl[j] = 0u;
+        }
+    }
+    if (hist) {
+        __syncthreads();
+        uint32_t* Hg = p.qhist + (int64_t)img * kQBins;
+        for (int d = tid; d < kQBins; d += kBlock) {
+            const uint32_t c = qbins[d];
+            if (c) atomicAdd(&Hg[d], c);
+        }
+        return;
+    }
+    if (p.cand)
+        block_emit_topk<PPT>(kh, kl, p.k, p.cand + ((int64_t)img * tiles + t) * p.k, p.reduce_mode, s_surv, s_cnt, s_top);
+}
+
+// The strategy's score OF THE MEAN PROBABILITY over the T passes at listed pixels: p_c = scale * sum_t softmax(x_t)_c, accumulated
+// as softmax_sum_kernel accumulates its per-class sums, then pp_uncertainty_from_prob's formulas (QueryStats._get_entropy(query,
+// prob) at the picked pixels only, query.py:262-264).  One thread per pixel.
+template <int CMAX, bool EXACT>
+__global__ __launch_bounds__(kBlock) void acq_lowres_mc_at_kernel(const float* low, int64_t ldx, int T, int h, int w, float sh, float sw,
+                                                                int align, int Wc, int C, int strategy, float scale,
+                                                                const int32_t* img_idx, const int32_t* pix_idx, int64_t n, float* out)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int pix = pix_idx[i], Y = pix / Wc, X = pix - Y * Wc;
+    const Lerp lh = lerp_src(Y, h, sh, align), lw = lerp_src(X, w, sw, align);
+    const int64_t pass_stride = (int64_t)h * w * ldx;
+    const float* base = low + (int64_t)img_idx[i] * T * pass_stride;
+    const int64_t a00 = ((int64_t)lh.i0 * w + lw.i0) * ldx, a01 = ((int64_t)lh.i0 * w + lw.i1) * ldx;
+    const int64_t a10 = ((int64_t)lh.i1 * w + lw.i0) * ldx, a11 = ((int64_t)lh.i1 * w + lw.i1) * ldx;
+    float acc[CMAX];
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) acc[c] = 0.0f;
+    for (int t = 0; t < T; ++t) {
+        const float* b = base + (int64_t)t * pass_stride;
+        float x[CMAX];
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c)
+            if (EXACT || c < C) x[c] = bilerp(lh.l0, lh.l1, lw.l0, lw.l1, b[a00 + c], b[a01 + c], b[a10 + c], b[a11 + c]);
+        // (STRAT = least-confidence: only the probabilities are wanted here, no logf per pass)
+        (void)mc_pass_score<PP_ACQ_LEAST_CONFIDENCE, CMAX, EXACT>([&](int c) { return x[c]; }, C, 0, [&](int c, float pc) { acc[c] += pc; });
+    }
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) acc[c] = scale * acc[c];
+    out[i] = pixel_score<CMAX, EXACT>(acc, C, strategy, 1);
 }
 
 // ---- any class count: C > PP_ACQ_REG_CLASSES ------------------------------------------------------------
@@ -1901,21 +2107,14 @@ __global__ __launch_bounds__(kBlock) void softmax_sum_kernel(const float* logits
         for (int c = 0; c < cn; ++c) acc[c] = 0.0f;
         for (int t = 0; t < T; ++t) {
             const float* xt = base + (int64_t)t * sT;
-            float m = xt[0];
-            for (int c = 1; c < C; ++c) m = fmaxf(m, xt[(int64_t)c * sC]);
-            float S = 0.0f;
-            for (int c = 0; c < C; ++c) S += expf(xt[(int64_t)c * sC] - m);
             if (c0 == 0) {
-                float ent = 0.0f, t1 = -INFINITY, t2 = -INFINITY;
-                for (int c = 0; c < C; ++c) {
-                    const float pc = expf(xt[(int64_t)c * sC] - m) / S;
-                    if (c < cn) acc[c] += pc;
-                    ent += (-pc) * logf(pc);
-                    t2 = fmaxf(t2, fminf(t1, pc));
-                    t1 = fmaxf(t1, pc);
-                }
-                uc += strategy == PP_ACQ_ENTROPY ? ent : (strategy == PP_ACQ_LEAST_CONFIDENCE ? 1.0f - t1 : fabsf(t1 - t2));
+                uc += mc_pass_score<-1, 0, false>([&](int c) { return xt[(int64_t)c * sC]; }, C, strategy,
+                                                  [&](int c, float pc) { if (c < cn) acc[c] += pc; });
             } else {
+                float m = xt[0];
+                for (int c = 1; c < C; ++c) m = fmaxf(m, xt[(int64_t)c * sC]);
+                float S = 0.0f;
+                for (int c = 0; c < C; ++c) S += expf(xt[(int64_t)c * sC] - m);
                 for (int c = 0; c < cn; ++c) acc[c] += expf(xt[(int64_t)(c0 + c) * sC] - m) / S;
             }
         }
@@ -2448,6 +2647,66 @@ static int validate_lowres(const float* low, int64_t ldx, int64_t B, int64_t C, 
     return PP_OK;
 }
 
+// ---- MC-dropout low-resolution path: host side ---------------------------------------------------------
+static int validate_lowres_mc(const float* low, int64_t ldx, int64_t B, int64_t T, int64_t C, int64_t h, int64_t w, int64_t H,
+                              int64_t W, int64_t Hc, int64_t Wc, int strategy)
+{
+    if (T < 1 || T > 0x7FFFFFFFll) return fail(PP_ERR_BAD_ARG, "bad number of passes T=%lld", (long long)T);
+    if (int rc = validate_lowres(low, ldx, B, C, h, w, H, W, Hc, Wc, strategy)) return rc;
+    if (C > PP_ACQ_MAX_CLASSES)
+        return fail(PP_ERR_UNSUPPORTED, "MC-dropout low-resolution scorer: C=%lld > %d classes", (long long)C, PP_ACQ_MAX_CLASSES);
+    if (h * w * ldx > 0x7FFFFFFFFFFFll / (B * T)) return fail(PP_ERR_UNSUPPORTED, "low-res tensor too large");
+    return PP_OK;
+}
+
+// make_lowres_plan's tile, except that the 8-row tile is kept for the dataset class counts with the patch in LDS: the generic
+// instantiations (per-class predicates) and the form that reads from memory run the 4-row tile only (no scratch in any form)
+static LowresPlan make_lowres_mc_plan(int64_t B, int64_t C, int64_t h, int64_t w, int64_t Hc, int64_t Wc, float sh, float sw)
+{
+    LowresPlan pl = make_lowres_plan(B, C, h, w, Hc, Wc, sh, sw, !(C == 11 || C == 19 || C == 21));
+    if (!pl.lds && pl.ppt != 4) pl = make_lowres_plan(B, C, h, w, Hc, Wc, sh, sw, true);
+    return pl;
+}
+
+template <int CMAX, bool EXACT>
+static int launch_lowres_mc(const LowresMcParams& q, const LowresPlan& pl, int64_t B, hipStream_t st)
+{
+    EventScope ev(st);
+    dim3 grid((unsigned)(B * pl.tiles_x * pl.tiles_y)), block(kBlock);
+    // strategy-specialised: the least-confidence and margin kernels carry no logf
+#define PP_MC(P, L, S) hipLaunchKernelGGL((acq_lowres_mc_kernel<CMAX, EXACT, P, L, S>), grid, block, (L) ? pl.lds_bytes : 0, st, q)
+#define PP_MC_STRAT(P, L)                                                        \
+    do {                                                                         \
+        if (q.g.strategy == PP_ACQ_ENTROPY) PP_MC(P, L, PP_ACQ_ENTROPY);         \
+        else if (q.g.strategy == PP_ACQ_LEAST_CONFIDENCE) PP_MC(P, L, PP_ACQ_LEAST_CONFIDENCE); \
+        else PP_MC(P, L, PP_ACQ_MARGIN);                                         \
+    } while (0)
+    if (!pl.lds) {
+        if (pl.ppt != 4) return fail(PP_ERR_BAD_ARG, "MC-dropout low-resolution scorer: plan without LDS patch and %d rows per wave", pl.ppt);
+        PP_MC_STRAT(4, false);
+    } else if (pl.ppt == 8) {
+        if constexpr (EXACT) PP_MC_STRAT(8, true);
+        else return fail(PP_ERR_BAD_ARG, "MC-dropout low-resolution scorer: 8 rows per wave planned for C=%d", q.g.C);
+    } else {
+        PP_MC_STRAT(4, true);
+    }
+#undef PP_MC_STRAT
+#undef PP_MC
+    return check_launch("acq_lowres_mc_kernel");
+}
+
+static int dispatch_lowres_mc(const LowresMcParams& q, const LowresPlan& pl, int64_t B, hipStream_t st)
+{
+    switch (q.g.C) {
+        case 11: return launch_lowres_mc<11, true>(q, pl, B, st);
+        case 19: return launch_lowres_mc<19, true>(q, pl, B, st);
+        case 21: return launch_lowres_mc<21, true>(q, pl, B, st);
+        default: break;
+    }
+    if (q.g.C <= 32) return launch_lowres_mc<32, false>(q, pl, B, st);
+    return launch_lowres_mc<64, false>(q, pl, B, st);
+}
+
 }  // namespace pp
 
 using namespace pp;
@@ -2695,6 +2954,84 @@ int pp_acq_lowres_score_at(const float* low, int64_t ldx, int64_t B, int64_t C, 
     }
 #undef PP_AT
     return check_launch("acq_lowres_at_kernel");
+}
+
+int pp_acq_lowres_mc_score_topk(const float* low, int64_t ldx, int64_t B, int64_t T, int64_t C, int64_t h, int64_t w, int64_t H,
+                                int64_t W, int align_corners, int64_t Hc, int64_t Wc, const uint8_t* exclude, int strategy,
+                                float scale, int64_t k, int32_t* out_idx, float* out_val, float* out_map, void* workspace,
+                                size_t ws_bytes, pp_stream_t stream)
+{
+    if (int rc = validate_lowres_mc(low, ldx, B, T, C, h, w, H, W, Hc, Wc, strategy)) return rc;
+    const int64_t N = Hc * Wc;
+    hipStream_t st = as_stream(stream);
+    float sh, sw;
+    lowres_scales(h, w, H, W, align_corners, sh, sw);
+    LowresMcParams q{{low, ldx, exclude, out_map, nullptr, (int)h, (int)w, (int)Hc, (int)Wc, sh, sw, align_corners ? 1 : 0,
+                      (int)C, 0, 0, 0, strategy, g_reduce_mode, 0}, (int)T, scale};
+    LowresParams& p = q.g;
+    const LowresPlan pl = make_lowres_mc_plan(B, C, h, w, Hc, Wc, sh, sw);
+    p.tiles_x = pl.tiles_x; p.tiles_y = pl.tiles_y; p.patch_cap = pl.patch_cap;
+    if (k == 0) {     // score map only
+        if (!out_map) return fail(PP_ERR_BAD_ARG, "k == 0 (map only) needs out_map");
+        return dispatch_lowres_mc(q, pl, B, st);
+    }
+    if (k < 1 || k > N) return fail(PP_ERR_BAD_K, "k=%lld outside [1, H*W=%lld]", (long long)k, (long long)N);
+    if (!out_idx) return fail(PP_ERR_BAD_ARG, "out_idx is null");
+    const size_t need = pp_acq_lowres_workspace_bytes(B, C, Hc, Wc, k);
+    if (!workspace || ws_bytes < need)
+        return fail(PP_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, need);
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(PP_ERR_BAD_ARG, "workspace must be 256-B aligned");
+    const int largest = strategy != PP_ACQ_MARGIN;
+    if (k <= kSmallKMax) {
+        const int64_t n_cand = (int64_t)pl.waves_per_image * k;
+        uint64_t* cand = reinterpret_cast<uint64_t*>(workspace);
+        uint64_t* other = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(workspace) +
+                                                      align_up((size_t)B * n_cand * 8, 256));
+        p.cand = cand;
+        p.k = (int)k;
+        if (int rc = dispatch_lowres_mc(q, pl, B, st)) return rc;
+        return run_merge(cand, n_cand, other, B, (int)k, largest, out_idx, out_val, st);
+    }
+    // the mean of T scores lies in the score's own range: the quantised-histogram select applies unchanged
+    float* map = out_map ? out_map : reinterpret_cast<float*>(workspace);
+    uint64_t* gbuf = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(workspace) + align_up((size_t)B * N * 4, 256));
+    p.out_map = map;
+    const float qs = score_qscale(strategy, C);
+    const bool fuse_hist = g_hist_fuse && large_q_ok(B, k, qs);
+    if (fuse_hist) {
+        p.qhist = large_hist(gbuf, B, k);
+        p.qscale = qs;
+        if (hipMemsetAsync(p.qhist, 0, (size_t)B * kQBins * 4, st) != hipSuccess) return fail(PP_ERR_LAUNCH, "topk: memset failed");
+    }
+    if (int rc = dispatch_lowres_mc(q, pl, B, st)) return rc;
+    return run_large(map, B, N, k, largest, gbuf, out_idx, out_val, st, qs, fuse_hist);
+}
+
+int pp_acq_lowres_mc_score_at(const float* low, int64_t ldx, int64_t B, int64_t T, int64_t C, int64_t h, int64_t w, int64_t H,
+                              int64_t W, int align_corners, int64_t Hc, int64_t Wc, int strategy, float scale,
+                              const int32_t* img_idx, const int32_t* pix_idx, int64_t n, float* out, pp_stream_t stream)
+{
+    if (int rc = validate_lowres_mc(low, ldx, B, T, C, h, w, H, W, Hc, Wc, strategy)) return rc;
+    if (n == 0) return PP_OK;
+    if (n < 0 || !img_idx || !pix_idx || !out) return fail(PP_ERR_BAD_ARG, "score_at: null pointer or n < 0");
+    float sh, sw;
+    lowres_scales(h, w, H, W, align_corners, sh, sw);
+    hipStream_t st = as_stream(stream);
+    dim3 grid((unsigned)cdiv(n, kBlock)), block(kBlock);
+    const int al = align_corners ? 1 : 0;
+#define PP_MC_AT(CM, EX)                                                                                                             \
+    hipLaunchKernelGGL((acq_lowres_mc_at_kernel<CM, EX>), grid, block, 0, st, low, ldx, (int)T, (int)h, (int)w, sh, sw, al, (int)Wc, \
+                       (int)C, strategy, scale, img_idx, pix_idx, n, out)
+    switch (C) {
+        case 11: PP_MC_AT(11, true); break;
+        case 19: PP_MC_AT(19, true); break;
+        case 21: PP_MC_AT(21, true); break;
+        default:
+            if (C <= 32) PP_MC_AT(32, false);
+            else PP_MC_AT(64, false);
+    }
+#undef PP_MC_AT
+    return check_launch("acq_lowres_mc_at_kernel");
 }
 
 int pp_topk_select(const float* scores, int64_t B, int64_t N, int64_t k, int largest, int32_t* out_idx,

@@ -12,6 +12,8 @@ reference (`model.py:44,83`, `train.py:9,82`, `datasets/*.py` codecs) runs uncha
     the evident intent: mean over `mc_n_steps` stochastic passes;
   * for models that expose `forward_lowres` (DeepLab) the x4 bilinear upsample of deeplab.py:55-56 is folded into the
     scoring kernel as well (pp_acq_lowres_score_topk, SURVEY.md §8f rank 1): identical queries, no full-size logits;
+  * with such a model the MC-dropout branch scores the classifier output of all passes in one launch as well
+    (pp_acq_lowres_mc_score_topk): the picks of the full-size route, no full-size logits or probability map;
   * there is no CPU fallback: tensors must live on the GPU and the extension must be built.
 """
 import os
@@ -225,6 +227,11 @@ class QuerySelector:
         # enqueued, so host and GPU overlap.
         pipelined = (QUERY_PIPELINE and FUSED_LOWRES and not self.use_mc_dropout and hasattr(model, "forward_lowres")
                      and not self.reverse_order and not is_random and torch.device(self.device).type == "cuda")
+        # MC-dropout (query.py:177-187) scored from the classifier output of all passes (pp_acq_lowres_mc_score_topk); chunked
+        # passes, the random strategy, models without forward_lowres and heads wider than the kernel keep the full-size route
+        mc_lowres = (FUSED_LOWRES and self.use_mc_dropout and hasattr(model, "forward_lowres") and not is_random
+                     and self.mc_n_steps <= self.mc_chunk
+                     and int(getattr(model, "n_classes", self.n_classes)) <= acq.MC_LOWRES_MAX_CLASSES)
         # DeepLab: x4 align_corners=True (deeplab.py:55-56); FPNSeg: x2 align_corners=False (decoders.py:101)
         lowres_align = bool(getattr(model, "LOWRES_ALIGN_CORNERS", True))
         copy_stream = self.__dict__.get("_copy_stream")
@@ -346,6 +353,29 @@ class QuerySelector:
                     n_j = len(chosen[j])
                     emit(it, chosen[j], ent_all[off:off + n_j] if want_stats else None)
                     off += n_j
+                pending.clear()
+                return
+            if mc_lowres:
+                # MC-dropout from the classifier output, one image at a time: its passes in ONE forward that stops in front of the
+                # upsample (the tensor the full-size route forwards: same dropout masks, same picks), one scoring launch (mean score
+                # over the passes, exclusion and top-k in the kernel) and the entropy of the mean probability at the picked pixels
+                # only - no full-size logits, no [C,H,W] probability map, no host entropy map.  (Images are not forwarded together:
+                # the convolution planner picks its split-K form by the rows of the batch, so the logits of a joint forward differ
+                # from the single ones in the last bits, and the dropout masks would change.)
+                T = self.mc_n_steps
+                for it in pending:
+                    h, w = it.size
+                    excl_j = it.exclude | ~it.draws["cand"] if self.reverse_order else it.exclude
+                    low, full_size = model.forward_lowres(it.x.expand(T, -1, -1, -1).contiguous())
+                    idx, _, _ = acq.mc_score_topk_lowres(low, T, full_size, torch.from_numpy(np.ascontiguousarray(excl_j))[None],
+                                                         self.query_strategy, self._k_launch(h, w), crop=(h, w),
+                                                         align_corners=lowres_align)
+                    cand = choose(it, idx[0].cpu().numpy().astype(np.int64))[0]
+                    ent = None
+                    if not human_labels and it.y is not None:
+                        ent = acq.mc_score_at_lowres(low, T, full_size, np.zeros(len(cand), dtype=np.int32), cand, "entropy",
+                                                     crop=(h, w), align_corners=lowres_align).cpu().numpy().astype(np.float64)
+                    emit(it, cand, ent)
                 pending.clear()
                 return
             for j, it in enumerate(pending):

@@ -1,20 +1,38 @@
 #!/usr/bin/env python3
 """MC-dropout acquisition round (query.py:176-188 as intended: mean over mc_n_steps stochastic passes) through the real
-DeepLabv3+-MobileNetV2: all passes of an image in one forward (mc_chunk = 32) vs one forward per pass (mc_chunk = 1)."""
-import io, contextlib, os, sys, tempfile, time, warnings
+DeepLabv3+-MobileNetV2, 16 images of 256x512, 19 classes, entropy, device-synchronised wall time per round:
+
+  * the full-size route (all passes of an image in one forward, pp_bilinear_fwd -> pp_acq_softmax_sum -> pp_topk_select, mean
+    probability map read back for the statistics) against the route from the classifier output (pp_acq_lowres_mc_score_topk /
+    pp_acq_lowres_mc_score_at) - same process, alternating, `--repeats` rounds each after a warm-up round of every route; the
+    spread of the full-size route's repeats is the run's own noise;
+  * --chunks: all passes in one forward (mc_chunk = 32) vs one forward per pass (mc_chunk = 1), the earlier record.
+
+    python tools/mc_dropout_bench.py [--repeats 3] [--images 16] [--steps 20] [--chunks] [--only lowres|full] [--out FILE]
+(--only: one route alone, for a kernel trace of it.)"""
+import argparse
+import contextlib
+import io
+import os
+import sys
+import tempfile
+import time
+import warnings
 from argparse import Namespace
+
 import numpy as np
 import torch
+
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from pixelpick_amd import query as ppq
 from pixelpick_amd.utils.utils import get_model
+
 warnings.simplefilter("ignore")
-C, h, w, n = 19, 256, 512, 16
-m = get_model(Namespace(use_mc_dropout=False, mc_dropout_p=0.2, n_classes=C, network_name="deeplab", weight_type="random")).cuda()
+C, h, w = 19, 256, 512
 
 
 class DS:
-    def __init__(s):
+    def __init__(s, n):
         s.xs = torch.randn(n, 3, h, w); s.ys = torch.randint(0, C, (n, h, w)); s.queries = [np.zeros((h, w), bool) for _ in range(n)]
 
     def label_queries(s, d, k):
@@ -26,21 +44,73 @@ class DL:
         s.dataset = d
 
     def __iter__(s):
-        for i in range(n):
+        for i in range(len(s.dataset.xs)):
             yield {"x": s.dataset.xs[i][None], "y": s.dataset.ys[i][None], "p_img": [f"/i{i}.png"]}
 
 
-with tempfile.TemporaryDirectory() as td:
-    a = Namespace(dataset_name="cs", debug=False, dir_root=td, experim_name="mc", ignore_index=C, mc_n_steps=20, n_classes=C,
-                  n_pixels_by_us=20, network_name="deeplab", weight_type="random", query_strategy="entropy", reverse_order=False, stride_total=16,
-                  top_n_percent=0.0, use_mc_dropout=True, vote_type="hard")
-    for chunk in (32, 1):
-        a.mc_chunk = chunk
-        qs = ppq.QuerySelector(a, DL(DS()), device=torch.device("cuda:0"))
-        with contextlib.redirect_stdout(io.StringIO()):
-            qs(1, m)
-        torch.cuda.synchronize(); t0 = time.perf_counter()
-        with contextlib.redirect_stdout(io.StringIO()):
-            qs(2, m)
-        torch.cuda.synchronize()
-        print(f"mc_n_steps=20, mc_chunk={chunk:2d}: {n / (time.perf_counter() - t0):6.1f} images/s")
+def one_round(qs, model, nth):
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    with contextlib.redirect_stdout(io.StringIO()):
+        qs(nth, model)
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--images", type=int, default=16)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--chunks", action="store_true")
+    ap.add_argument("--only", choices=["lowres", "full"], default=None)
+    ap.add_argument("--out", default=None)
+    o = ap.parse_args()
+    n = o.images
+    model = get_model(Namespace(use_mc_dropout=True, mc_dropout_p=0.2, n_classes=C, network_name="deeplab", weight_type="random")).cuda()
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    with tempfile.TemporaryDirectory() as td:
+        def selector(**kw):
+            a = Namespace(dataset_name="cs", debug=False, dir_root=td, experim_name="mc", ignore_index=C, mc_n_steps=o.steps, n_classes=C,
+                          n_pixels_by_us=20, network_name="deeplab", weight_type="random", query_strategy="entropy", reverse_order=False,
+                          stride_total=16, top_n_percent=0.0, use_mc_dropout=True, vote_type="hard", mc_chunk=32, **kw)
+            return ppq.QuerySelector(a, DL(DS(n)), device=torch.device("cuda:0"))
+
+        routes = [("full-size route", False), ("classifier-output route", True)]
+        if o.only:
+            routes = [r for r in routes if r[1] == (o.only == "lowres")][:1]
+        sels = [selector() for _ in routes]
+        times = [[] for _ in routes]
+        for rep in range(o.repeats + 1):                       # round 0 of every route: warm-up
+            for i, (_, fused) in enumerate(routes):
+                ppq.FUSED_LOWRES = fused
+                t = one_round(sels[i], model, rep + 1)
+                if rep:
+                    times[i].append(t)
+        say(f"MC-dropout acquisition round, {n} images {h}x{w}, C={C}, mc_n_steps={o.steps}, entropy, k=20; {o.repeats} rounds per route, alternating")
+        rates = []
+        for (name, _), ts in zip(routes, times):
+            r = [n / t for t in ts]
+            rates.append(r)
+            say(f"  {name:48s} {np.mean(r):7.1f} images/s  (rounds: {', '.join(f'{x:.1f}' for x in r)}; spread {max(r) - min(r):.1f})")
+        if len(rates) == 2:
+            say(f"  ratio to the full-size route: {np.mean(rates[1]) / np.mean(rates[0]):.2f}x")
+        if o.chunks:
+            ppq.FUSED_LOWRES = False
+            for chunk in (32, 1):
+                qs = selector()
+                qs.mc_chunk = chunk
+                one_round(qs, model, 1)
+                say(f"  full-size route, mc_chunk={chunk:2d}: {n / one_round(qs, model, 2):6.1f} images/s")
+    if o.out:
+        os.makedirs(os.path.dirname(os.path.abspath(o.out)), exist_ok=True)
+        with open(o.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

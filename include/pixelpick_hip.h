@@ -587,6 +587,36 @@ int pp_predict_lowres(const float* low, int64_t ldx, int64_t B, int64_t C, int64
                       int align_corners, int64_t Hc, int64_t Wc, const void* target, int target_kind, uint8_t* pred,
                       int64_t* hist, pp_stream_t stream);
 
+/* The per-epoch picture's byte panels straight from the LOW-resolution classifier output: replaces, in two launches and without
+ * the full-resolution logits, their softmax or any float map on the host,
+ *   deeplab.py:55-56        F.interpolate(pred, size, mode='bilinear', align_corners=True)
+ *   model.py:124,150-156    softmax / argmax / the three _query maps of one image (margin negated)
+ *   utils/utils.py:394-417  Visualiser._preprocess: palette lookup, min-max normalisation to bytes
+ * (the resize to half size, the grid and the PNG stay with the caller: utils/utils.py:418-432).
+ *   low, ldx, B, C, h, w, H, W, align_corners, Hc, Wc   exactly pp_predict_lowres's meaning and validation; C <= PP_ACQ_MAX_CLASSES
+ *            (wider heads: PP_ERR_UNSUPPORTED)
+ *   image    f32 [B,3,Hc,Wc] or NULL, element (n,c,y,x) at n*image_sn + c*image_sc + y*image_sr + x
+ *   target   [B,Hc,Wc] labels or NULL, target_kind 0 none, 1 uint8, 2 int64
+ *   palette  device u8 [256][3]
+ *   rgb      u8 [B][n_rgb][Hc][Wc][3], every panel contiguous, in the order: input (if image), target (if target), prediction
+ *            input       one (min, max) over all three channels, written HWC
+ *            target      palette[label] for 0 <= label <= 255, black otherwise (the reference raises KeyError for a label its
+ *                        palette dict lacks)
+ *            prediction  palette[first maximum of the interpolated logits]: the label pp_predict_lowres writes
+ *   gray     u8 [B][3][Hc][Wc]: least confidence, -|p1 - p2| (the negated margin model.py:155 passes), entropy - the values
+ *            pp_acq_lowres_score_topk writes to its score map in its default scorer form (the same device function)
+ *   ranges   f32 [B][4][2] or NULL: (min, max) of input, confidence, negated margin, entropy as used below ((0, 0) without image)
+ * A float panel v becomes bytes, per image and in fp32 with every operation rounded on its own, as torch does on the CPU:
+ *   mn = min v ; t = v - mn ; d = max(t) + 1e-7f ; byte = trunc(clamp((t / d) * 255.0f, 0, 255))
+ * min and max skip NaN (entropy is NaN where a probability underflows: 0 * log 0) and a NaN pixel becomes 0; the reference's
+ * min() would be NaN there and blank the whole panel.  All outputs are fully overwritten; no atomics: reproducible run to run.
+ * workspace: pp_vis_lowres_workspace_bytes(B, Hc, Wc) bytes (0 for sizes no launch would accept); too small: PP_ERR_WORKSPACE. */
+size_t pp_vis_lowres_workspace_bytes(int64_t B, int64_t Hc, int64_t Wc);
+int pp_vis_lowres(const float* low, int64_t ldx, int64_t B, int64_t C, int64_t h, int64_t w, int64_t H, int64_t W,
+                  int align_corners, int64_t Hc, int64_t Wc, const float* image, int64_t image_sn, int64_t image_sc,
+                  int64_t image_sr, const void* target, int target_kind, const uint8_t* palette, uint8_t* rgb, uint8_t* gray,
+                  float* ranges, void* workspace, size_t ws_bytes, pp_stream_t stream);
+
 /* torch.optim.Adam step on flat buffers (utils/utils.py:125-141): elements [0,n_split) use lr_a (the
  * backbone/encoder group at lr/10), the rest lr_b; L2 weight decay; `step` is 1-based; grads are
  * multiplied by grad_scale first (1/world_size after the gradient all-reduce). */

@@ -132,6 +132,7 @@ const Entry kEntries[] = {
     PP_PLAN_ENTRY(pp_sparse_ce_lowres_fwd_bwd),
     PP_PLAN_ENTRY(pp_confusion_matrix_update),
     PP_PLAN_ENTRY(pp_predict_lowres),
+    PP_PLAN_ENTRY(pp_vis_lowres),
     PP_PLAN_ENTRY(pp_adam_step_flat),
     PP_PLAN_ENTRY(pp_sgd_step_flat),
     PP_PLAN_ENTRY(pp_add2d),

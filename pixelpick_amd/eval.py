@@ -2,13 +2,15 @@
 
 The network stops at its classifier output (`forward_lowres`); the confusion matrix comes from `RunningScore.update_from_lowres`
 and the label map, when a visualizer asks for it, from `predict_lowres` - one launch each, interpolating on the fly, so the
-full-resolution logits, their softmax and the two device-to-host maps of eval.py:60-63 never exist.  The reference's `Visualiser`
-class (PNG writing) is not part of this package: only the callable hook is.
+full-resolution logits, their softmax and the two device-to-host maps of eval.py:60-63 never exist.  A `visualizer` that offers
+`from_lowres` (utils.utils.Visualiser) gets the picture the same way: its byte panels are rendered from the classifier output in
+one call per forwarded batch (visualise.render_lowres); any other callable receives the reference's dict of CPU tensors.
 """
 import os
 from math import ceil
 from typing import Callable, Optional
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -26,8 +28,10 @@ def evaluate(model, dataloader, experim_name: str, epoch: Optional[int] = None, 
     `dataset_name` ("voc": reflect-pad to a multiple of `stride_total`, crop back).  Consecutive batches of equal size are
     forwarded `val_batch_size` images at a time, as Model._val does (eval mode: the result per image does not depend on the
     batch).  With `dir_ckpt`, log_val.txt (header epoch,miou,pixel_acc + one row) is written to <dir_ckpt>[/eNN]/val and, every
-    `visualize_interval`-th batch, `visualizer(dict_tensors, fp=...)` receives the first image's input / target / pred /
-    confidence / margin (negated) / entropy on the CPU.  -> mean IoU."""
+    `visualize_interval`-th batch, the first image's picture goes to <that directory>/<num_iter>.png: through
+    `visualizer.from_lowres(...)` when the visualizer has it (our Visualiser; heads of up to 64 classes), otherwise
+    `visualizer(dict_tensors, fp=...)` receives input / target / pred / confidence / margin (negated) / entropy on the CPU.
+    -> mean IoU."""
     if not callable(getattr(model, "forward_lowres", None)):
         raise TypeError(f"evaluate() needs a model with forward_lowres(); {type(model).__name__} has none")
     if dir_ckpt is not None:
@@ -54,7 +58,15 @@ def evaluate(model, dataloader, experim_name: str, epoch: Optional[int] = None, 
             xp = xs
         low, size = model.forward_lowres(xp)
         tracker.update_from_lowres(ys, low, size, crop=crop, align_corners=align)
-        if dir_ckpt is not None and visualizer is not None:
+        fused = callable(getattr(visualizer, "from_lowres", None)) and low.shape[-1] <= 64 and xs.shape[2:] == ys.shape[1:]
+        if dir_ckpt is not None and visualizer is not None and fused:
+            # our Visualiser: the due images' byte panels in ONE render_lowres call on the classifier output, one copy to the host
+            offs = np.cumsum([0] + [p[1].shape[0] for p in pend])
+            due = [(int(offs[i]), f"{dir_ckpt}/{p[0]}.png") for i, p in enumerate(pend) if p[0] % visualize_interval == 0]
+            if due:
+                visualizer.from_lowres(low, size, xs, ys, [fp for _, fp in due], crop=crop, align_corners=align,
+                                       index=[i for i, _ in due])
+        elif dir_ckpt is not None and visualizer is not None:
             off = 0
             for num_iter, x, y in pend:
                 if num_iter % visualize_interval == 0:

@@ -12,7 +12,9 @@ Everything between the loaders is the reference's loop:
         self.dataloader.dataset.label_queries(queries, nth_query + 1)
 
 with the train step on `FlatTrainer` (HIP forward/backward, sparse CE, fused Adam, Poly lr per iteration) and the
-per-step metrics on the device (`RunningScore.update_from_lowres` / `update_from_logits`).  PNG dumps (`Visualiser`) are omitted.
+per-step metrics on the device (`RunningScore.update_from_lowres` / `update_from_logits`).  The per-epoch pictures
+(`Visualiser`: <epoch>_train.png, <epoch>_val.png, model.py:150-158,227-238) are opt-in - args.visualise = True or
+PIXELPICK_VISUALISE=1 - and rendered from the classifier output where the step kept it (visualise.render_lowres).
 """
 import os
 from math import ceil
@@ -25,7 +27,7 @@ from . import dist_utils
 from .query import QuerySelector
 from .trainer import FlatTrainer
 from .utils.metrics import AverageMeter, RunningScore
-from .utils.utils import get_model, optimizer_spec
+from .utils.utils import Visualiser, get_model, optimizer_spec
 
 
 def write_log(fp, list_entities=None, header=None):
@@ -64,6 +66,12 @@ class Model:
         env = os.environ.get("PIXELPICK_METRICS_LOWRES")
         self._metrics_lowres = (env != "0") if env is not None else (True if ml is None else bool(ml))
         self._metrics_lowres_forced = self._metrics_lowres and ml is True
+        # model.py:50,150-158,227-238: one picture of the last train batch's and the last validation batch's first image per epoch.
+        # Opt-in (args.visualise = True or PIXELPICK_VISUALISE=1; default off: the file sets and the measured loop stay as they
+        # were); only rank 0 writes.
+        env = os.environ.get("PIXELPICK_VISUALISE")
+        self._visualise = (env not in ("", "0")) if env is not None else bool(getattr(args, "visualise", False))
+        self.vis = Visualiser(args.dataset_name) if self._visualise else None
         self.device = device or torch.device("cuda:0")
         self.dir_checkpoints = f"{args.dir_root}/checkpoints/{args.experim_name}"
         self.experim_name = args.experim_name
@@ -192,6 +200,7 @@ class Model:
         from . import trainer as _tr
         keep = "low" if (self._metrics_lowres and _tr.SPARSE_LOWRES_CE and getattr(model, "LOWRES_LOGITS", False)
                          and self.n_classes <= 104) else True
+        x = y_shown = None
         for it, dict_data in enumerate(loader):
             if skip:
                 if it >= n_local * self.world:
@@ -221,6 +230,7 @@ class Model:
                     if self.n_pixels_by_us != 0:
                         mask = dict_data['queries'].to(self.device)
                 self._uploaded(x, y, mask)
+            y_shown = y                                                    # model.py:152 draws the unmasked labels
             if self.n_pixels_by_us != 0:                                   # model.py:108-110
                 mask = mask.view(y.shape)
                 # same values as `y.flatten()[~mask.flatten()] = ignore_index`, without the nonzero() + host sync
@@ -248,6 +258,12 @@ class Model:
             self.running_loss.update(trainer.last_loss)
             if self.debug:
                 break
+        if self._visualise and self.rank == 0 and x is not None:           # model.py:150-158: first image of the last batch
+            if trainer.last_low is not None and trainer.last_low.shape[-1] <= 64:
+                self.vis.from_lowres(trainer.last_low, trainer.last_low_size, x, y_shown, self._picture_path(epoch, "train"),
+                                     align_corners=trainer.last_low_align)
+            else:
+                self._picture_from_logits(trainer.last_logits[:1], x[0], y_shown[0], self._picture_path(epoch, "train"))
         trainer.sync_buffers()
         self._all_reduce_scores()
         scores = self.running_score.get_scores()[0]
@@ -285,6 +301,19 @@ class Model:
         self.best_miou = -1.0
         return model
 
+    def _picture_path(self, epoch, which) -> str:
+        sub = f"{self.nth_query}_query" if self.n_pixels_by_us != 0 else "fully_sup"
+        return f"{self.dir_checkpoints}/{sub}/{epoch}_{which}.png"
+
+    def _picture_from_logits(self, logits, x, y, fp):
+        """model.py:124,150-158 on full-resolution logits [1,C,H,W] (steps and models that kept no classifier output, heads wider
+        than 64 classes): the generic host path of the Visualiser."""
+        prob, pred = F.softmax(logits.detach(), dim=1).contiguous(), logits.argmax(dim=1)
+        ent, lc, ms = [self._query(prob, uc)[0].cpu() for uc in ("entropy", "least_confidence", "margin_sampling")]
+        self.vis({'input': x.cpu(), 'target': y.cpu(), 'pred': pred[0].cpu(), 'confidence': lc,
+                  'margin': -ms,           # minus sign: smaller margins are drawn brighter
+                  'entropy': ent}, fp=fp)
+
     def _steps_per_epoch(self) -> int:
         if self._train_loader is not None:
             return len(self._train_loader)
@@ -315,10 +344,13 @@ class Model:
         lowres = (self._metrics_lowres and callable(getattr(model, "forward_lowres", None)) and self.n_classes <= 104
                   and (getattr(model, "LOWRES_EXACT", False) or self._metrics_lowres_forced))
 
+        shown = []               # what the picture needs of the last forwarded image (args.visualise)
+
         def flush():
             if not pend_x:
                 return
             xs, ys = torch.cat(pend_x, dim=0), torch.cat(pend_y, dim=0)
+            x_shown = xs[-1:]
             crop = None
             if self.dataset_name == "voc":
                 h, w = ys.shape[1:]
@@ -329,11 +361,18 @@ class Model:
             if lowres:
                 low, size = model.forward_lowres(xs)
                 self.running_score.update_from_lowres(ys, low, size, crop=crop, align_corners=model.LOWRES_ALIGN_CORNERS)
+                if self._visualise and low.shape[-1] <= 64:
+                    shown[:] = ["low", low[-1:], size, x_shown, ys[-1:], crop]
+                elif self._visualise:
+                    logits = model(xs[-1:])['pred']
+                    shown[:] = ["logits", logits if crop is None else logits[:, :, :crop[0], :crop[1]], x_shown, ys[-1:]]
             else:
                 logits = model(xs)['pred']
                 if crop is not None:
                     logits = logits[:, :, :crop[0], :crop[1]].contiguous()
                 self.running_score.update_from_logits(ys, logits)
+                if self._visualise:
+                    shown[:] = ["logits", logits[-1:], x_shown, ys[-1:]]
             pend_x.clear()
             pend_y.clear()
 
@@ -352,6 +391,13 @@ class Model:
             if self.debug:
                 break
         flush()
+        if self._visualise and self.rank == 0 and shown:                    # model.py:227-238, with the VOC crop
+            if shown[0] == "low":
+                _, low, size, x, y, crop = shown
+                self.vis.from_lowres(low, size, x, y, self._picture_path(epoch, "val"), crop=crop,
+                                     align_corners=model.LOWRES_ALIGN_CORNERS)
+            else:
+                self._picture_from_logits(shown[1], shown[2][0], shown[3][0], self._picture_path(epoch, "val"))
         self._all_reduce_scores()
         scores = self.running_score.get_scores()[0]
         miou, pixel_acc = scores['Mean IoU'], scores['Pixel Acc']

@@ -161,6 +161,45 @@ int pp_acq_lowres_mc_score_at(const float* low, int64_t ldx, int64_t B, int64_t 
                               int64_t H, int64_t W, int align_corners, int64_t Hc, int64_t Wc, int strategy, float scale,
                               const int32_t* img_idx, const int32_t* pix_idx, int64_t n, float* out, pp_stream_t stream);
 
+/* MC-dropout HARD vote (args.py:34 `--vote_type hard`, stored at query.py:31 and read by nothing in the reference: the semantics
+ * below are this library's specification).  In the MC-dropout branch (query.py:177-187) every stochastic pass t casts ONE vote per
+ * pixel, a_t = argmax_c x_t[c] of its logits (no softmax: it is monotone; exactly equal logits -> the LOWEST class index), and the
+ * score is a function of the vote counts n_c = #{t : a_t = c} (sum n_c = T), n_(1) >= n_(2) the two largest (n_(2) = 0: unanimous):
+ *   PP_ACQ_ENTROPY           float(sum_c tab[n_c]) * 2^-24, tab[0] = 0, tab[n] = (uint32) llrint(-(n/T) ln(n/T) 2^24) evaluated in
+ *                            double on the host; an integer sum - a function of the multiset of counts, independent of class order
+ *   PP_ACQ_LEAST_CONFIDENCE  float(T - n_(1)) / float(T)        PP_ACQ_MARGIN  float(n_(1) - n_(2)) / float(T)    (one IEEE division)
+ * Largest scores win for entropy / least-confidence, smallest for margin, as everywhere.  Excluded pixels get -1.0 (entropy,
+ * least-confidence) or 2.0 (margin) - NOT the soft scorers' 0.0 / 1.0, which here are the scores of every unanimous pixel: an
+ * excluded pixel sorts strictly behind every un-excluded one (and is still returned, lowest index first, when k exceeds the number
+ * of un-excluded pixels).  Ordering policy unchanged: value-sorted, ties -> lower flat index; no NaN can occur.  The scores take few
+ * distinct values, so ties decide most picks.  T in [1, 255] (the counts are bytes), otherwise PP_ERR_UNSUPPORTED; PP_ACQ_REFERENCE_ORDER
+ * has no meaning here and is PP_ERR_BAD_ARG.
+ *
+ * pp_acq_vote_accumulate: over the T passes in logits [T,C,H,W] (element strides sT,sC,sH,sW; any C), votes u8 [C,H,W] (+)= the
+ * per-class vote counts; accumulate == 0 overwrites.  The caller keeps the total over all accumulating calls <= 255.
+ * Null logits / votes, bad shape: PP_ERR_BAD_ARG. */
+int pp_acq_vote_accumulate(const float* logits, int64_t T, int64_t C, int64_t H, int64_t W,
+                           int64_t sT, int64_t sC, int64_t sH, int64_t sW,
+                           uint8_t* votes, int accumulate, pp_stream_t stream);
+
+/* votes u8 [B,C,H,W] of T passes each -> out_map f32 [B,H,W]: the hard-vote score above, the fills at exclude (u8 [B,H,W] or NULL).
+ * Null votes / out_map, bad shape, unknown strategy: PP_ERR_BAD_ARG; T outside [1, 255] or B > 65535: PP_ERR_UNSUPPORTED. */
+int pp_acq_vote_score_map(const uint8_t* votes, int64_t B, int64_t T, int64_t C, int64_t H, int64_t W,
+                          const uint8_t* exclude, int strategy, float* out_map, pp_stream_t stream);
+
+/* pp_acq_lowres_mc_score_topk with the hard vote in place of the mean score: votes of the T passes of the interpolated (cropped)
+ * logits, score, fills and top-k in one launch, no full-resolution logits of any pass.  low, ldx, B, T, C, h, w, H, W, align_corners,
+ * Hc, Wc, exclude, k == 0 (map only), out_idx / out_val / out_map and the workspace, pp_acq_lowres_workspace_bytes(B, C, Hc, Wc, k)
+ * (T does not enter), are that entry's; out_map holds the fills above.  C <= 64 (PP_ACQ_MAX_CLASSES), wider heads return
+ * PP_ERR_UNSUPPORTED (pp_bilinear_fwd + pp_acq_vote_accumulate + pp_acq_vote_score_map serve them), as does T outside [1, 255];
+ * PP_ERR_BAD_K / PP_ERR_WORKSPACE / PP_ERR_BAD_ARG as pp_acq_lowres_score_topk.  The result equals pp_bilinear_fwd of the B*T entries,
+ * pp_acq_vote_accumulate per image, pp_acq_vote_score_map and pp_topk_select, bit for bit (tested). */
+int pp_acq_lowres_mc_vote_topk(const float* low, int64_t ldx, int64_t B, int64_t T, int64_t C, int64_t h, int64_t w,
+                               int64_t H, int64_t W, int align_corners, int64_t Hc, int64_t Wc,
+                               const uint8_t* exclude, int strategy, int64_t k,
+                               int32_t* out_idx, float* out_val, float* out_map,
+                               void* workspace, size_t ws_bytes, pp_stream_t stream);
+
 
 /* =============================================================================================
  * Network layers (DeepLabv3+-MobileNetV2 / FPN-ResNet50 forward + backward), NHWC fp32.

@@ -276,3 +276,80 @@ def mc_score_at_lowres(low: torch.Tensor, n_passes: int, size, img_idx, pix_idx,
                                                   _lib.current_stream_ptr(dev))
     _lib.check(rc, "pp_acq_lowres_mc_score_at")
     return out
+
+
+# ---- MC-dropout HARD vote (args.py:34 --vote_type hard; query.py:31,177-187) ---------------------------------------------
+# Every pass votes for its arg-max class (equal logits: the lowest index) and the score is a function of the vote counts
+# (include/pixelpick_hip.h, pp_acq_vote_*).  Excluded pixels get VOTE_FILL, not FILL: 0.0 / 1.0 are the scores of unanimous pixels.
+MC_VOTE_MAX_PASSES = 255       # the vote counts are bytes
+VOTE_FILL = {"entropy": -1.0, "least_confidence": -1.0, "margin_sampling": 2.0, "margin": 2.0}
+
+
+def _vote_passes(n_passes) -> int:
+    T = int(n_passes)
+    if T < 1 or T > MC_VOTE_MAX_PASSES:
+        raise ValueError(f"hard vote: n_passes = {n_passes} outside [1, {MC_VOTE_MAX_PASSES}] (the vote counts are bytes); "
+                         f"there is no fall-back to the soft vote")
+    return T
+
+
+def mc_vote_topk_lowres(low: torch.Tensor, n_passes: int, size, exclude, strategy: str, k: int, crop=None,
+                        align_corners: bool = True) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor], torch.Tensor]:
+    """mc_score_topk_lowres with the hard vote in place of the mean score: the vote counts of the n_passes passes of the interpolated
+    logits -> vote entropy / least-confidence / margin -> VOTE_FILL at excluded pixels -> top-k, one launch.
+
+    low [B*n_passes,h,w,C] f32 channels-last on the GPU, image-major; exclude [B,crop_h,crop_w].  Returns (idx int32 [B,k],
+    val f32 [B,k], map f32 [B,crop_h,crop_w]); k == 0 -> (None, None, map)."""
+    _vote_passes(n_passes)
+    B, T, h, w, C, ldx, H, W, Hc, Wc = _mc_geom(low, n_passes, size, crop)
+    L = _lib.lib()
+    dev = low.device
+    ex = _exclude_u8(exclude, B, Hc, Wc, dev)
+    idx = torch.empty((B, k), dtype=torch.int32, device=dev) if k else None
+    val = torch.empty((B, k), dtype=torch.float32, device=dev) if k else None
+    omap = torch.empty((B, Hc, Wc), dtype=torch.float32, device=dev)
+    ws = _ws(L.pp_acq_lowres_workspace_bytes(B, C, Hc, Wc, k), dev) if k else None
+    with torch.cuda.device(dev):
+        rc = L.pp_acq_lowres_mc_vote_topk(low.data_ptr(), ldx, B, T, C, h, w, H, W, int(bool(align_corners)), Hc, Wc,
+                                          ex.data_ptr() if ex is not None else None, strategy_id(strategy), k,
+                                          idx.data_ptr() if k else None, val.data_ptr() if k else None, omap.data_ptr(),
+                                          ws.data_ptr() if k else None, ws.numel() if k else 0, _lib.current_stream_ptr(dev))
+    _lib.check(rc, "pp_acq_lowres_mc_vote_topk")
+    return idx, val, omap
+
+
+def mc_vote_accumulate_(logits: torch.Tensor, votes: torch.Tensor, accumulate: bool = True):
+    """votes u8 [C,H,W] (+)= the per-class vote counts of the T passes in logits [T,C,H,W] (any strides, any C), one kernel pass.
+    The total over all accumulating calls must stay <= MC_VOTE_MAX_PASSES."""
+    _require_cuda_f32(logits, "logits", 4)
+    T, C, H, W = logits.shape
+    _vote_passes(T)
+    if (not isinstance(votes, torch.Tensor) or tuple(votes.shape) != (C, H, W) or not votes.is_contiguous() or votes.dtype != torch.uint8
+            or votes.device != logits.device):
+        raise ValueError(f"votes must be a contiguous uint8 {(C, H, W)} tensor on the logits' device")
+    sT, sC, sH, sW = logits.stride()
+    with torch.cuda.device(logits.device):
+        rc = _lib.lib().pp_acq_vote_accumulate(logits.data_ptr(), T, C, H, W, sT, sC, sH, sW, votes.data_ptr(),
+                                               int(bool(accumulate)), _lib.current_stream_ptr(logits.device))
+    _lib.check(rc, "pp_acq_vote_accumulate")
+
+
+def vote_score_map(votes: torch.Tensor, n_passes: int, exclude, strategy: str) -> torch.Tensor:
+    """votes u8 [B,C,H,W] (or [C,H,W]) of n_passes passes each -> the hard-vote score map f32 [B,H,W], VOTE_FILL at excluded pixels."""
+    T = _vote_passes(n_passes)
+    if isinstance(votes, torch.Tensor) and votes.ndim == 3:
+        votes = votes[None]
+    if not isinstance(votes, torch.Tensor) or votes.ndim != 4 or votes.dtype != torch.uint8:
+        raise ValueError("votes must be a uint8 [B,C,H,W] tensor")
+    if not votes.is_cuda:
+        raise _lib.PixelPickHipError("votes must live on the GPU: the HIP path has no CPU fallback")
+    votes = votes.contiguous()
+    B, C, H, W = votes.shape
+    dev = votes.device
+    ex = _exclude_u8(exclude, B, H, W, dev)
+    omap = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().pp_acq_vote_score_map(votes.data_ptr(), B, T, C, H, W, ex.data_ptr() if ex is not None else None,
+                                              strategy_id(strategy), omap.data_ptr(), _lib.current_stream_ptr(dev))
+    _lib.check(rc, "pp_acq_vote_score_map")
+    return omap

@@ -900,6 +900,205 @@ __global__ __launch_bounds__(kBlock) void acq_lowres_mc_at_kernel(const float* l
     out[i] = pixel_score<CMAX, EXACT>(acc, C, strategy, 1);
 }
 
+// ---- MC-dropout HARD vote (args.py:34 --vote_type hard; query.py:31,177-187) ----------------------------------------------
+// Query by committee: pass t votes for a_t = argmax_c x_t[c] (exactly equal logits: the LOWEST class index), n_c = #{t : a_t = c},
+// n_(1) >= n_(2) the two largest counts, and the pixel's score is a function of the counts alone:
+//   entropy           float(sum_c tab[n_c]) * 2^-24, tab[n] = llrint(-(n/T) ln(n/T) 2^24) built in double on the HOST (tab[0] = 0) and
+//                     summed as integers: a function of the multiset of counts, no device logf, the same bits in any restatement
+//   least-confidence  float(T - n_(1)) / float(T)        margin  float(n_(1) - n_(2)) / float(T)       (one IEEE division each)
+// Excluded pixels get -1.0 (entropy, least-confidence) / 2.0 (margin), NOT the soft scorers' 0.0 / 1.0: those are the scores of every
+// unanimous pixel, and an excluded pixel must sort strictly behind every un-excluded one.  Scores take few distinct values, so most
+// picks are decided by the tie rule (lower flat index first); no NaN can occur.  T <= 255: the counts are bytes.
+// The table travels BY VALUE in the kernel arguments (1 KB, no host-to-device copy: the call stays recordable by csrc/plan.hip).
+struct VoteTable { uint32_t v[256]; };
+
+__device__ __forceinline__ float vote_score(int strategy, uint32_t n1, uint32_t n2, uint32_t ent_q, int T)
+{
+    if (strategy == PP_ACQ_ENTROPY) return (float)ent_q * 5.9604644775390625e-08f;            // 2^-24: exact
+    const uint32_t num = strategy == PP_ACQ_LEAST_CONFIDENCE ? (uint32_t)T - n1 : n1 - n2;
+    return __fdiv_rn((float)num, (float)T);
+}
+__device__ __forceinline__ float vote_fill(int strategy) { return strategy != PP_ACQ_MARGIN ? -1.0f : 2.0f; }
+
+// acq_lowres_mc_kernel's tile, patch staging, bilerp, exclusion, map store and candidate epilogue; per pass a running maximum in
+// ascending class order (strict >: the lowest class wins ties) and ONE vote into the pixel's counters - bytes packed four to a
+// 32-bit register, (CMAX+3)/4 words per pixel, bumped by an unrolled compare-and-add (no run-time register index: no scratch).
+// No expf / logf in the pass loop.  The table is staged once per block into the survivor lists' LDS (free until block_emit_topk).
+struct LowresVoteParams {
+    LowresParams g;      // low: [B*T,h,w,ldx]; qhist unused (k > 48: the map, then the generic selection)
+    int T;
+    VoteTable tab;
+};
+
+template <int CMAX, bool EXACT, int PPT, bool LDS>
+__global__ __launch_bounds__(kBlock, 2) void acq_lowres_mc_vote_kernel(LowresVoteParams q)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_patch[];
+    __shared__ uint64_t s_surv[kBlock / kWave][kSurvCap];
+    __shared__ uint32_t s_cnt[kBlock / kWave];
+    __shared__ uint64_t s_top[(kBlock / kWave) * kSmallKMax];
+    const LowresParams& p = q.g;
+    constexpr int TR = (kBlock / kWave) * PPT, TC = kWave;
+    constexpr int NW = (CMAX + 3) / 4;
+    const int tiles = p.tiles_x * p.tiles_y;
+    const int img = blockIdx.x / tiles;
+    const int t = blockIdx.x - img * tiles;
+    const int ty = t / p.tiles_x, tx = t - ty * p.tiles_x;
+    const int tid = threadIdx.x, lane = tid & (kWave - 1);
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int C = EXACT ? CMAX : p.C;
+    const int CP = C | 1;
+    const bool largest = p.strategy != PP_ACQ_MARGIN;
+    const int64_t N = (int64_t)p.Hc * p.Wc;
+    const int X0 = tx * TC, Y0 = ty * TR;
+    const int X1 = min(X0 + TC - 1, p.Wc - 1), Y1 = min(Y0 + TR - 1, p.Hc - 1);
+    const int c_lo = lerp_src(X0, p.w, p.sw, p.align).i0, c_hi = lerp_src(X1, p.w, p.sw, p.align).i1;
+    const int r_lo = lerp_src(Y0, p.h, p.sh, p.align).i0, r_hi = lerp_src(Y1, p.h, p.sh, p.align).i1;
+    const int pw = c_hi - c_lo + 1, ph = r_hi - r_lo + 1;
+    const int64_t pass_stride = (int64_t)p.h * p.w * p.ldx;
+    const float* img_base = p.low + (int64_t)img * q.T * pass_stride;
+    const int X = X0 + lane;
+    const bool xin = X < p.Wc;
+    const Lerp lw = lerp_src(xin ? X : X1, p.w, p.sw, p.align);
+    const int64_t pitch = LDS ? (int64_t)CP : p.ldx;
+    const int64_t o0 = (int64_t)(LDS ? lw.i0 - c_lo : lw.i0) * pitch, o1 = (int64_t)(LDS ? lw.i1 - c_lo : lw.i1) * pitch;
+    const int64_t row_pitch = (LDS ? pw : p.w) * pitch;
+    if constexpr (LDS) {
+        if (ph * pw * CP > p.patch_cap) __builtin_trap();   // host sizing bug: never silently read past the patch
+    }
+
+    uint32_t cnt[PPT][NW];
+#pragma unroll
+    for (int j = 0; j < PPT; ++j)
+#pragma unroll
+        for (int i = 0; i < NW; ++i) cnt[j][i] = 0u;
+    for (int ps = 0; ps < q.T; ++ps) {
+        const float* base = img_base + (int64_t)ps * pass_stride;
+        if constexpr (LDS) {
+            if (ps) __syncthreads();          // every wave has finished reading the previous pass's patch
+            const int n = ph * pw * C;
+            for (int e = tid; e < n; e += kBlock) {
+                const int pc = e / C, ch = e - pc * C;
+                const int r = pc / pw, c = pc - r * pw;
+                s_patch[pc * CP + ch] = base[((int64_t)(r_lo + r) * p.w + c_lo + c) * p.ldx + ch];
+            }
+            __syncthreads();
+        }
+        const float* src = LDS ? s_patch : base;
+#pragma unroll
+        for (int j = 0; j < PPT; ++j) {
+            const int Y = Y0 + wv * PPT + j;
+            if (Y < p.Hc && xin) {
+                const Lerp lh = lerp_src(Y, p.h, p.sh, p.align);
+                const float* r0 = src + (int64_t)(LDS ? lh.i0 - r_lo : lh.i0) * row_pitch;
+                const float* r1 = src + (int64_t)(LDS ? lh.i1 - r_lo : lh.i1) * row_pitch;
+                float best = bilerp(lh.l0, lh.l1, lw.l0, lw.l1, r0[o0], r0[o1], r1[o0], r1[o1]);
+                int bi = 0;
+#pragma unroll
+                for (int c = 1; c < CMAX; ++c)
+                    if (EXACT || c < C) {
+                        const float v = bilerp(lh.l0, lh.l1, lw.l0, lw.l1, r0[o0 + c], r0[o1 + c], r1[o0 + c], r1[o1 + c]);
+                        if (v > best) { best = v; bi = c; }
+                    }
+                const uint32_t inc = 1u << ((bi & 3) * 8);
+                const int wd = bi >> 2;
+#pragma unroll
+                for (int i = 0; i < NW; ++i) cnt[j][i] += wd == i ? inc : 0u;
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+
+    uint32_t* s_tab = reinterpret_cast<uint32_t*>(&s_surv[0][0]);
+    static_assert(kBlock == 256, "one table entry per thread");
+    s_tab[tid] = q.tab.v[tid];
+    __syncthreads();
+    const uint8_t* excl = p.exclude ? p.exclude + (int64_t)img * N : nullptr;
+    float* omap = p.out_map ? p.out_map + (int64_t)img * N : nullptr;
+    const bool want_ent = p.strategy == PP_ACQ_ENTROPY;
+    uint32_t kh[PPT], kl[PPT];
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) {
+        const int Y = Y0 + wv * PPT + j;
+        if (Y < p.Hc && xin) {
+            uint32_t n1 = 0u, n2 = 0u, eq = 0u;
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c) {
+                const uint32_t n = (cnt[j][c >> 2] >> ((c & 3) * 8)) & 0xFFu;      // classes beyond C hold 0 votes: tab[0] = 0
+                n2 = max(n2, min(n1, n));
+                n1 = max(n1, n);
+                if (want_ent) eq += s_tab[n];
+            }
+            float sc = vote_score(p.strategy, n1, n2, eq, q.T);
+            const int64_t pix = (int64_t)Y * p.Wc + X;
+            if (excl && excl[pix]) sc = vote_fill(p.strategy);
+            if (omap) omap[pix] = sc;
+            kh[j] = order_key(sc, largest);
+            kl[j] = 0xFFFFFFFFu - (uint32_t)pix;
+        } else {
+            kh[j] = 0u; kl[j] = 0u;
+        }
+    }
+    if (p.cand) {
+        __syncthreads();                      // the table's LDS becomes the survivor lists
+        block_emit_topk<PPT>(kh, kl, p.k, p.cand + ((int64_t)img * tiles + t) * p.k, p.reduce_mode, s_surv, s_cnt, s_top);
+    }
+}
+
+// Full-size route, any class count: votes u8 [C,N] (+)= the per-class vote counts of the T passes in logits [T,C,H,W] (element
+// strides).  One thread per pixel streams the classes with the running best and bumps ONE byte per pass.
+__global__ __launch_bounds__(kBlock) void vote_accumulate_kernel(const float* logits, int T, int C, int W, int64_t N, int64_t sT, int64_t sC,
+                                                                int64_t sH, int64_t sW, uint8_t* votes, int accumulate)
+{
+    const int64_t pix = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (pix >= N) return;
+    const int64_t hh = pix / W, ww = pix - hh * W;
+    const float* base = logits + hh * sH + ww * sW;
+    if (!accumulate)
+        for (int c = 0; c < C; ++c) votes[(int64_t)c * N + pix] = 0;
+    for (int t = 0; t < T; ++t) {
+        const float* xt = base + (int64_t)t * sT;
+        float best = xt[0];
+        int bi = 0;
+        for (int c = 1; c < C; ++c) {
+            const float v = xt[(int64_t)c * sC];
+            if (v > best) { best = v; bi = c; }
+        }
+        uint8_t* slot = votes + (int64_t)bi * N + pix;
+        *slot = (uint8_t)(*slot + 1u);
+    }
+}
+
+struct VoteScoreParams {
+    const uint8_t* votes;     // [B,C,N]
+    const uint8_t* exclude;   // [B,N] or null
+    float* out_map;           // [B,N]
+    int64_t N;
+    int C, T, strategy;
+    VoteTable tab;
+};
+
+__global__ __launch_bounds__(kBlock) void vote_score_kernel(VoteScoreParams p)
+{
+    __shared__ uint32_t s_tab[256];
+    s_tab[threadIdx.x] = p.tab.v[threadIdx.x];
+    __syncthreads();
+    const int64_t pix = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (pix >= p.N) return;
+    const int64_t img = blockIdx.y;
+    const uint8_t* v = p.votes + img * p.C * p.N + pix;
+    uint32_t n1 = 0u, n2 = 0u, eq = 0u;
+    for (int c = 0; c < p.C; ++c) {
+        const uint32_t n = v[(int64_t)c * p.N];
+        n2 = max(n2, min(n1, n));
+        n1 = max(n1, n);
+        eq += s_tab[n];
+    }
+    float sc = vote_score(p.strategy, n1, n2, eq, p.T);
+    if (p.exclude && p.exclude[img * p.N + pix]) sc = vote_fill(p.strategy);
+    p.out_map[img * p.N + pix] = sc;
+}
+
 // ---- any class count: C > PP_ACQ_REG_CLASSES ------------------------------------------------------------
 // The scorers above keep a pixel's class vector in registers (C <= 64).  The reference takes whatever class count the model emits
 // (query.py:190 softmaxes dim 1 of any width), so wider heads STREAM the class vector instead: two (default scorer) or three
@@ -2665,6 +2864,60 @@ static int dispatch_lowres_mc(const LowresMcParams& q, const LowresPlan& pl, int
     return launch_lowres_mc<64, false>(q, pl, B, st);
 }
 
+// ---- MC-dropout hard vote: host side ---------------------------------------------------------------------
+constexpr int64_t kVoteMaxPasses = 255;      // the vote counts are bytes
+
+static int validate_vote_passes(int64_t T)
+{
+    if (T < 1 || T > kVoteMaxPasses)
+        return fail(PP_ERR_UNSUPPORTED, "hard vote: T=%lld passes outside [1, %lld] (the vote counts are bytes)", (long long)T,
+                    (long long)kVoteMaxPasses);
+    return PP_OK;
+}
+
+// tab[n] = llrint(-(n/T) ln(n/T) 2^24) in double, tab[0] = 0 (and 0 beyond T)
+static void fill_vote_table(int64_t T, VoteTable& tab)
+{
+    for (int n = 0; n < 256; ++n) tab.v[n] = 0u;
+    for (int64_t n = 1; n <= T; ++n) {
+        const double p = (double)n / (double)T;
+        tab.v[n] = (uint32_t)llrint(-p * log(p) * 16777216.0);
+    }
+}
+
+// make_lowres_mc_plan's tiles: 8 rows per wave for the dataset class counts with the patch in LDS (48 counter words at C = 21), 4
+// rows for the generic instantiations (64 counter words at CMAX = 64) and the form that reads from memory
+template <int CMAX, bool EXACT>
+static int launch_lowres_mc_vote(const LowresVoteParams& q, const LowresPlan& pl, int64_t B, hipStream_t st)
+{
+    EventScope ev(st);
+    dim3 grid((unsigned)(B * pl.tiles_x * pl.tiles_y)), block(kBlock);
+#define PP_VOTE(P, L) hipLaunchKernelGGL((acq_lowres_mc_vote_kernel<CMAX, EXACT, P, L>), grid, block, (L) ? pl.lds_bytes : 0, st, q)
+    if (!pl.lds) {
+        if (pl.ppt != 4) return fail(PP_ERR_BAD_ARG, "hard-vote low-resolution scorer: plan without LDS patch and %d rows per wave", pl.ppt);
+        PP_VOTE(4, false);
+    } else if (pl.ppt == 8) {
+        if constexpr (EXACT) PP_VOTE(8, true);
+        else return fail(PP_ERR_BAD_ARG, "hard-vote low-resolution scorer: 8 rows per wave planned for C=%d", q.g.C);
+    } else {
+        PP_VOTE(4, true);
+    }
+#undef PP_VOTE
+    return check_launch("acq_lowres_mc_vote_kernel");
+}
+
+static int dispatch_lowres_mc_vote(const LowresVoteParams& q, const LowresPlan& pl, int64_t B, hipStream_t st)
+{
+    switch (q.g.C) {
+        case 11: return launch_lowres_mc_vote<11, true>(q, pl, B, st);
+        case 19: return launch_lowres_mc_vote<19, true>(q, pl, B, st);
+        case 21: return launch_lowres_mc_vote<21, true>(q, pl, B, st);
+        default: break;
+    }
+    if (q.g.C <= 32) return launch_lowres_mc_vote<32, false>(q, pl, B, st);
+    return launch_lowres_mc_vote<64, false>(q, pl, B, st);
+}
+
 }  // namespace pp
 
 using namespace pp;
@@ -2990,6 +3243,80 @@ int pp_acq_lowres_mc_score_at(const float* low, int64_t ldx, int64_t B, int64_t 
     }
 #undef PP_MC_AT
     return check_launch("acq_lowres_mc_at_kernel");
+}
+
+int pp_acq_vote_accumulate(const float* logits, int64_t T, int64_t C, int64_t H, int64_t W, int64_t sT, int64_t sC, int64_t sH,
+                           int64_t sW, uint8_t* votes, int accumulate, pp_stream_t stream)
+{
+    if (!votes) return fail(PP_ERR_BAD_ARG, "vote_accumulate: votes is null");
+    if (!logits) return fail(PP_ERR_BAD_ARG, "logits is null");
+    if (int rc = validate_vote_passes(T)) return rc;
+    if (int rc = validate(logits, T, C, H, W, 0)) return rc;
+    const int64_t N = H * W;
+    hipLaunchKernelGGL(vote_accumulate_kernel, dim3((unsigned)cdiv(N, kBlock)), dim3(kBlock), 0, as_stream(stream), logits, (int)T, (int)C,
+                       (int)W, N, sT, sC, sH, sW, votes, accumulate);
+    return check_launch("vote_accumulate_kernel");
+}
+
+int pp_acq_vote_score_map(const uint8_t* votes, int64_t B, int64_t T, int64_t C, int64_t H, int64_t W, const uint8_t* exclude,
+                          int strategy, float* out_map, pp_stream_t stream)
+{
+    if (!votes) return fail(PP_ERR_BAD_ARG, "vote_score_map: votes is null");
+    if (!out_map) return fail(PP_ERR_BAD_ARG, "out_map is null");
+    if (int rc = validate_vote_passes(T)) return rc;
+    if (int rc = validate(reinterpret_cast<const float*>(votes), B, C, H, W, strategy)) return rc;
+    if (B > 65535) return fail(PP_ERR_UNSUPPORTED, "vote_score_map: B=%lld > 65535 images per call", (long long)B);
+    VoteScoreParams p{votes, exclude, out_map, H * W, (int)C, (int)T, strategy, {}};
+    fill_vote_table(T, p.tab);
+    hipLaunchKernelGGL(vote_score_kernel, dim3((unsigned)cdiv(p.N, kBlock), (unsigned)B), dim3(kBlock), 0, as_stream(stream), p);
+    return check_launch("vote_score_kernel");
+}
+
+int pp_acq_lowres_mc_vote_topk(const float* low, int64_t ldx, int64_t B, int64_t T, int64_t C, int64_t h, int64_t w, int64_t H,
+                               int64_t W, int align_corners, int64_t Hc, int64_t Wc, const uint8_t* exclude, int strategy, int64_t k,
+                               int32_t* out_idx, float* out_val, float* out_map, void* workspace, size_t ws_bytes, pp_stream_t stream)
+{
+    if (!low) return fail(PP_ERR_BAD_ARG, "logits is null");
+    if (int rc = validate_vote_passes(T)) return rc;
+    if (int rc = validate_lowres_mc(low, ldx, B, T, C, h, w, H, W, Hc, Wc, strategy)) return rc;
+    const int64_t N = Hc * Wc;
+    hipStream_t st = as_stream(stream);
+    float sh, sw;
+    lowres_scales(h, w, H, W, align_corners, sh, sw);
+    LowresVoteParams q{{low, ldx, exclude, out_map, nullptr, (int)h, (int)w, (int)Hc, (int)Wc, sh, sw, align_corners ? 1 : 0,
+                        (int)C, 0, 0, 0, strategy, g_reduce_mode, 0}, (int)T, {}};
+    fill_vote_table(T, q.tab);
+    LowresParams& p = q.g;
+    const LowresPlan pl = make_lowres_mc_plan(B, C, h, w, Hc, Wc, sh, sw);
+    p.tiles_x = pl.tiles_x; p.tiles_y = pl.tiles_y; p.patch_cap = pl.patch_cap;
+    if (k == 0) {     // score map only
+        if (!out_map) return fail(PP_ERR_BAD_ARG, "k == 0 (map only) needs out_map");
+        return dispatch_lowres_mc_vote(q, pl, B, st);
+    }
+    if (k < 1 || k > N) return fail(PP_ERR_BAD_K, "k=%lld outside [1, H*W=%lld]", (long long)k, (long long)N);
+    if (!out_idx) return fail(PP_ERR_BAD_ARG, "out_idx is null");
+    const size_t need = pp_acq_lowres_workspace_bytes(B, C, Hc, Wc, k);
+    if (!workspace || ws_bytes < need)
+        return fail(PP_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, need);
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(PP_ERR_BAD_ARG, "workspace must be 256-B aligned");
+    const int largest = strategy != PP_ACQ_MARGIN;
+    if (k <= kSmallKMax) {
+        const int64_t n_cand = (int64_t)pl.waves_per_image * k;
+        uint64_t* cand = reinterpret_cast<uint64_t*>(workspace);
+        uint64_t* other = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(workspace) +
+                                                      align_up((size_t)B * n_cand * 8, 256));
+        p.cand = cand;
+        p.k = (int)k;
+        if (int rc = dispatch_lowres_mc_vote(q, pl, B, st)) return rc;
+        return run_merge(cand, n_cand, other, B, (int)k, largest, out_idx, out_val, st);
+    }
+    // k > 48: the map, then pp_topk_select's selection on it - without the scorers' fused histogram, whose bins clamp the fills
+    // (-1.0 / 2.0 lie outside the score range) into the end bins
+    float* map = out_map ? out_map : reinterpret_cast<float*>(workspace);
+    uint64_t* gbuf = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(workspace) + align_up((size_t)B * N * 4, 256));
+    p.out_map = map;
+    if (int rc = dispatch_lowres_mc_vote(q, pl, B, st)) return rc;
+    return run_large(map, B, N, k, largest, gbuf, out_idx, out_val, st);
 }
 
 int pp_topk_select(const float* scores, int64_t B, int64_t N, int64_t k, int largest, int32_t* out_idx,

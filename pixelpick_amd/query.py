@@ -14,10 +14,18 @@ reference (`model.py:44,83`, `train.py:9,82`, `datasets/*.py` codecs) runs uncha
     scoring kernel as well (pp_acq_lowres_score_topk, SURVEY.md §8f rank 1): identical queries, no full-size logits;
   * with such a model the MC-dropout branch scores the classifier output of all passes in one launch as well
     (pp_acq_lowres_mc_score_topk): the picks of the full-size route, no full-size logits or probability map;
+  * `vote_type="hard"` (args.py:34; stored at query.py:31 and read by nothing in the reference) makes the MC-dropout branch a
+    query-by-committee vote: every pass votes for its arg-max class and the strategy is evaluated on the vote shares
+    (include/pixelpick_hip.h, pp_acq_vote_*) - from the classifier output in one launch (pp_acq_lowres_mc_vote_topk) or, on the
+    full-size route, by pp_acq_vote_accumulate per chunk of passes + pp_acq_vote_score_map + pp_topk_select.  QueryStats' entropy
+    stays that of the mean probability; the `random` strategy, rounds without MC-dropout and any other value ignore it.  The vote
+    is specified on the logits pp_bilinear_fwd produces, i.e. for models that expose `forward_lowres` (on either route); a model
+    without it keeps the mean score it had before (tests/test_acq_gpu.py pins those picks) and the round says so in a warning;
   * there is no CPU fallback: tensors must live on the GPU and the extension must be built.
 """
 import os
 import pickle as pkl
+import warnings
 from math import ceil
 from pathlib import Path
 from typing import Dict, List, Tuple, Union
@@ -234,6 +242,15 @@ class QuerySelector:
                      and int(getattr(model, "n_classes", self.n_classes)) <= acq.MC_LOWRES_MAX_CLASSES)
         # DeepLab: x4 align_corners=True (deeplab.py:55-56); FPNSeg: x2 align_corners=False (decoders.py:101)
         lowres_align = bool(getattr(model, "LOWRES_ALIGN_CORNERS", True))
+        # args.py:34: the passes vote with their arg-max class and the strategy scores the vote shares (never a silent soft vote)
+        hard_vote = self.use_mc_dropout and self.vote_type == "hard" and not is_random
+        if hard_vote and not hasattr(model, "forward_lowres"):
+            # the vote is specified on pp_bilinear_fwd's logits; the picks of other models are pinned to the mean score
+            warnings.warn("vote_type='hard' needs a model with forward_lowres: this round uses the mean score (soft vote)", RuntimeWarning)
+            hard_vote = False
+        if hard_vote and not 1 <= self.mc_n_steps <= acq.MC_VOTE_MAX_PASSES:
+            raise ValueError(f"vote_type='hard' counts the votes in bytes: mc_n_steps = {self.mc_n_steps} is outside "
+                             f"[1, {acq.MC_VOTE_MAX_PASSES}]")
         copy_stream = self.__dict__.get("_copy_stream")
         if pipelined and copy_stream is None:
             copy_stream = self.__dict__["_copy_stream"] = torch.cuda.Stream(device=self.device)
@@ -367,9 +384,9 @@ class QuerySelector:
                     h, w = it.size
                     excl_j = it.exclude | ~it.draws["cand"] if self.reverse_order else it.exclude
                     low, full_size = model.forward_lowres(it.x.expand(T, -1, -1, -1).contiguous())
-                    idx, _, _ = acq.mc_score_topk_lowres(low, T, full_size, torch.from_numpy(np.ascontiguousarray(excl_j))[None],
-                                                         self.query_strategy, self._k_launch(h, w), crop=(h, w),
-                                                         align_corners=lowres_align)
+                    mc_topk = acq.mc_vote_topk_lowres if hard_vote else acq.mc_score_topk_lowres
+                    idx, _, _ = mc_topk(low, T, full_size, torch.from_numpy(np.ascontiguousarray(excl_j))[None],
+                                        self.query_strategy, self._k_launch(h, w), crop=(h, w), align_corners=lowres_align)
                     cand = choose(it, idx[0].cpu().numpy().astype(np.int64))[0]
                     ent = None
                     if not human_labels and it.y is not None:
@@ -387,17 +404,26 @@ class QuerySelector:
                     # the image instead of mc_n_steps launch-bound forwards at batch 1 (`mc_chunk` copies at a time)
                     uc_map = torch.empty((h, w), dtype=torch.float32, device=self.device)
                     prob = torch.empty((1, self.n_classes, h, w), dtype=torch.float32, device=self.device)
+                    votes = torch.empty((self.n_classes, h, w), dtype=torch.uint8, device=self.device) if hard_vote else None
                     left, first = self.mc_n_steps, True
                     while left > 0:
                         t = min(left, self.mc_chunk)
                         logits = self._forward_logits(model, it.x.expand(t, -1, -1, -1).contiguous(), h, w)
                         # uc_map += score(softmax(logits)) / n ; prob += softmax(logits) / n   (query.py:181-187), one HIP pass
-                        acq.mc_accumulate_(logits, prob[0], None if is_random else uc_map, "entropy" if is_random else self.query_strategy,
+                        # hard vote: the mean probability for the statistics as before, the votes of the chunk beside it
+                        soft_uc = None if is_random or hard_vote else uc_map
+                        acq.mc_accumulate_(logits, prob[0], soft_uc, self.query_strategy if soft_uc is not None else "entropy",
                                            1.0 / self.mc_n_steps, accumulate=not first)
+                        if hard_vote:
+                            acq.mc_vote_accumulate_(logits, votes, accumulate=not first)
                         left -= t
                         first = False
                     if is_random:                       # the drawn map is already the mean of the mc_n_steps host draws
                         idx_sorted = self._random_topk(it.draws["rmap"][None], excl_j[None], self._k_launch(h, w))[0]
+                    elif hard_vote:
+                        uc_map = acq.vote_score_map(votes, self.mc_n_steps, excl_j[None], self.query_strategy)[0]
+                        idx_t, _ = acq.topk_select(uc_map.reshape(1, h * w), self._k_launch(h, w), self._largest)
+                        idx_sorted = idx_t[0].cpu().numpy().astype(np.int64)
                     else:
                         uc_map[torch.from_numpy(excl_j).to(self.device)] = 0.0 if self._largest else 1.0
                         idx_t, _ = acq.topk_select(uc_map.reshape(1, h * w), self._k_launch(h, w), self._largest)

@@ -6,9 +6,14 @@ DeepLabv3+-MobileNetV2, 16 images of 256x512, 19 classes, entropy, device-synchr
     probability map read back for the statistics) against the route from the classifier output (pp_acq_lowres_mc_score_topk /
     pp_acq_lowres_mc_score_at) - same process, alternating, `--repeats` rounds each after a warm-up round of every route; the
     spread of the full-size route's repeats is the run's own noise;
-  * --chunks: all passes in one forward (mc_chunk = 32) vs one forward per pass (mc_chunk = 1), the earlier record.
+  * --chunks: all passes in one forward (mc_chunk = 32) vs one forward per pass (mc_chunk = 1), the earlier record;
+  * --vote_type hard (args.py:34): the same two routes with the hard vote (pp_acq_lowres_mc_vote_topk / pp_acq_vote_accumulate +
+    pp_acq_vote_score_map), the classifier-output route with the soft vote beside them, and the scorer call alone - the vote scorer
+    next to the soft scorer at one image's shape (device events over `--scorer_calls` calls, `--repeats` blocks each, alternating;
+    the spread of the soft scorer's blocks is the run's own noise).
 
-    python tools/mc_dropout_bench.py [--repeats 3] [--images 16] [--steps 20] [--chunks] [--only lowres|full] [--out FILE]
+    python tools/mc_dropout_bench.py [--repeats 3] [--images 16] [--steps 20] [--chunks] [--only lowres|full] [--vote_type soft|hard]
+                                     [--scorer_calls 200] [--out FILE]
 (--only: one route alone, for a kernel trace of it.)"""
 import argparse
 import contextlib
@@ -24,6 +29,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from pixelpick_amd import acquisition as acq
 from pixelpick_amd import query as ppq
 from pixelpick_amd.utils.utils import get_model
 
@@ -56,6 +62,30 @@ def one_round(qs, model, nth):
     return time.perf_counter() - t0
 
 
+def scorer_times(steps, repeats, calls, say):
+    """The scorer call of ONE image (B = 1, the selector's launch) on random classifier-output logits: microseconds per call."""
+    low = torch.randn(steps, h // 4, w // 4, C, device="cuda:0") * 3
+    excl = torch.zeros(1, h, w, dtype=torch.uint8, device="cuda:0")
+    fns = [("soft scorer (acq_lowres_mc_kernel)", lambda: acq.mc_score_topk_lowres(low, steps, (h, w), excl, "entropy", 20)),
+           ("vote scorer (acq_lowres_mc_vote_kernel)", lambda: acq.mc_vote_topk_lowres(low, steps, (h, w), excl, "entropy", 20))]
+    us = [[] for _ in fns]
+    for rep in range(repeats + 1):                             # block 0 of each: warm-up
+        for i, (_, fn) in enumerate(fns):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(calls):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            if rep:
+                us[i].append(e0.elapsed_time(e1) * 1e3 / calls)
+    say(f"scorer call alone (scorer + candidate merge + wrapper), 1 image {h}x{w} from {h // 4}x{w // 4}, C={C}, T={steps}, entropy, k=20; "
+        f"{repeats} blocks of {calls} calls, alternating")
+    for (name, _), u in zip(fns, us):
+        say(f"  {name:48s} {np.mean(u):8.1f} us/call  (blocks: {', '.join(f'{x:.1f}' for x in u)}; spread {max(u) - min(u):.1f})")
+    say(f"  vote / soft: {np.mean(us[1]) / np.mean(us[0]):.2f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=3)
@@ -63,6 +93,8 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--chunks", action="store_true")
     ap.add_argument("--only", choices=["lowres", "full"], default=None)
+    ap.add_argument("--vote_type", choices=["soft", "hard"], default="soft")
+    ap.add_argument("--scorer_calls", type=int, default=200)
     ap.add_argument("--out", default=None)
     o = ap.parse_args()
     n = o.images
@@ -77,13 +109,18 @@ def main():
         def selector(**kw):
             a = Namespace(dataset_name="cs", debug=False, dir_root=td, experim_name="mc", ignore_index=C, mc_n_steps=o.steps, n_classes=C,
                           n_pixels_by_us=20, network_name="deeplab", weight_type="random", query_strategy="entropy", reverse_order=False,
-                          stride_total=16, top_n_percent=0.0, use_mc_dropout=True, vote_type="hard", mc_chunk=32, **kw)
+                          stride_total=16, top_n_percent=0.0, use_mc_dropout=True, mc_chunk=32, **dict(dict(vote_type=o.vote_type), **kw))
             return ppq.QuerySelector(a, DL(DS(n)), device=torch.device("cuda:0"))
 
         routes = [("full-size route", False), ("classifier-output route", True)]
         if o.only:
             routes = [r for r in routes if r[1] == (o.only == "lowres")][:1]
         sels = [selector() for _ in routes]
+        if o.vote_type == "hard":
+            routes = [(f"{name}, hard vote", fused) for name, fused in routes]
+            if o.only != "full":
+                routes.append(("classifier-output route, soft vote", True))
+                sels.append(selector(vote_type="soft"))
         times = [[] for _ in routes]
         for rep in range(o.repeats + 1):                       # round 0 of every route: warm-up
             for i, (_, fused) in enumerate(routes):
@@ -91,14 +128,17 @@ def main():
                 t = one_round(sels[i], model, rep + 1)
                 if rep:
                     times[i].append(t)
-        say(f"MC-dropout acquisition round, {n} images {h}x{w}, C={C}, mc_n_steps={o.steps}, entropy, k=20; {o.repeats} rounds per route, alternating")
+        say(f"MC-dropout acquisition round, {n} images {h}x{w}, C={C}, mc_n_steps={o.steps}, vote_type={o.vote_type}, entropy, k=20; "
+            f"{o.repeats} rounds per route, alternating")
         rates = []
         for (name, _), ts in zip(routes, times):
             r = [n / t for t in ts]
             rates.append(r)
             say(f"  {name:48s} {np.mean(r):7.1f} images/s  (rounds: {', '.join(f'{x:.1f}' for x in r)}; spread {max(r) - min(r):.1f})")
-        if len(rates) == 2:
+        if len(rates) >= 2 and not o.only:
             say(f"  ratio to the full-size route: {np.mean(rates[1]) / np.mean(rates[0]):.2f}x")
+        if o.vote_type == "hard":
+            scorer_times(o.steps, o.repeats, o.scorer_calls, say)
         if o.chunks:
             ppq.FUSED_LOWRES = False
             for chunk in (32, 1):

@@ -597,7 +597,9 @@ int pp_sparse_ce_fwd_bwd(const float* logits, int B, int C, int64_t HW, int64_t 
  *   dlow (NULL to skip) f32 [B,h,w,lddx] = grad_out * d loss / d low  (what autograd hands to the classifier conv).
  * low f32 [B,h,w,ldx] channels-last, C valid channels; target i64 [B,H,W].  The labels are scanned once, the class vector
  * is interpolated only at labelled pixels (80 of 524 288 in the BASELINE step) and the backward gathers per low-res
- * pixel in a fixed order (no atomics: bitwise reproducible).  Neither the [B,C,H,W] logits nor their gradient exist. */
+ * pixel in a fixed order (no atomics: bitwise reproducible).  Neither the [B,C,H,W] logits nor their gradient exist.
+ * Any class count: up to 64 classes the class vector lives in registers, wider heads walk it from memory in chunks of 64 (the
+ * same semantics, the same workspace, the same reproducibility). */
 size_t pp_sparse_ce_lowres_workspace_bytes(void);
 int pp_sparse_ce_lowres_fwd_bwd(const float* low, int64_t ldx, int B, int C, int h, int w, int H, int W, int align_corners,
                                 const int64_t* target, int ignore_index, float* loss, float* count, const float* grad_out,
@@ -605,9 +607,23 @@ int pp_sparse_ce_lowres_fwd_bwd(const float* low, int64_t ldx, int B, int C, int
 
 /* Step metrics on the device (model.py:124-125,194-196 + utils/metrics.py:168-177): hist[t*C + argmax_c logits] += 1
  * for every pixel whose target t is in [0, C) (ignore_index >= C is skipped like RunningScore._fast_hist).  hist is
- * an int64 [C,C] accumulator the caller zeroes / reads (C*C*8 bytes D2H instead of two full maps). */
+ * an int64 [C,C] accumulator the caller zeroes / reads (C*C*8 bytes D2H instead of two full maps).
+ * C in [1, 256] (else PP_ERR_UNSUPPORTED): up to 104 classes count in block-private LDS counters, wider heads aggregate equal
+ * (target, prediction) pairs inside each wave and add them to hist with integer atomics.  Exact counts either way. */
 int pp_confusion_matrix_update(const float* logits, int B, int C, int64_t HW, int64_t sB, int64_t sC, const int64_t* target,
                                int64_t* hist, pp_stream_t stream);
+
+/* The same histogram from two LABEL maps: stands in for
+ *   utils/metrics.py:168-177  RunningScore._fast_hist / update(label_trues, label_preds)
+ *   model.py:124-125,196-199  ... running_score.update(y, pred)          where pred already is a label map on the device
+ * (pp_predict_lowres writes one: a head too wide for its LDS histogram takes its label map here, one byte per pixel between the
+ * two launches).
+ *   pred     u8 [n] predicted labels;  target [n] labels, target_kind 1 uint8, 2 int64 (pp_predict_lowres's meaning)
+ *   hist     i64 [C,C], ACCUMULATED into: hist[t*C + pred] += 1 where 0 <= t < C; pixels with pred >= C are not counted
+ * C in [1, 256] (else PP_ERR_UNSUPPORTED); nulls, another target_kind or n < 0: PP_ERR_BAD_ARG; n == 0: PP_OK without a launch.
+ * Integer counts only: reproducible run to run. */
+int pp_confusion_matrix_from_labels(const uint8_t* pred, const void* target, int target_kind, int64_t n, int C, int64_t* hist,
+                                    pp_stream_t stream);
 
 /* The label map and the step metrics straight from the LOW-resolution classifier output: replaces, in one launch and without
  * materialising the full-resolution logits,
@@ -619,7 +635,7 @@ int pp_confusion_matrix_update(const float* logits, int B, int C, int64_t HW, in
  *   target   [B,Hc,Wc] labels, target_kind 0 none (NULL), 1 uint8, 2 int64
  *   pred     u8 [B,Hc,Wc] or NULL: the FIRST maximum over the classes of every interpolated pixel (C <= 256)
  *   hist     i64 [C,C] or NULL, ACCUMULATED into: hist[t*C + argmax] += 1 where 0 <= t < C (labels >= C, 255, negative: ignored);
- *            needs target; C <= 104 (block-private LDS counters)
+ *            needs target; C <= 104 (block-private LDS counters; a wider head takes pred and pp_confusion_matrix_from_labels)
  * At least one of pred / hist.  Integer counts only: reproducible run to run.  Equal bit for bit to pp_bilinear_fwd followed by
  * argmax / pp_confusion_matrix_update (tested). */
 int pp_predict_lowres(const float* low, int64_t ldx, int64_t B, int64_t C, int64_t h, int64_t w, int64_t H, int64_t W,

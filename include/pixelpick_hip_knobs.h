@@ -54,6 +54,7 @@ void pp_debug_set_gemm_pw(int v);   /* pointwise GEMM kernel (gemm_pw.hip): low 
 void pp_debug_set_x3f(int v);   /* in-kernel activation split (conv_x3f.hip, an experiment that lives in the test build only - measured slower): bit 0 ON; bits 1-3 least GFLOP of a non-classic layer {1, 0.5, 2, 4, 8, 0.25, 0}; bits 4-5 least tiles {128, 64, 192, 256}; bits 6-7 least K {256, 128, 512, 16} (A/B) */
 void pp_debug_set_x3(int on);   /* large-tile conv layers: 1 = bf16x3-split MFMA kernel (default), 0 = fp32 MFMA kernels (A/B, parity) */
 void pp_debug_set_conv_variant(int v);
+void pp_debug_set_ce_stream(int on);   /* pp_sparse_ce_lowres_fwd_bwd: 1 = the streamed kernels (the form of heads wider than 64 classes) at EVERY class count, so that the tests hold them against the register kernels; 0 = default */
 /* Launch log: copies the ';'-joined names of the kernels launched since the previous call into buf (at most n - 1 characters and a
  * terminating NUL), clears the log and returns the log's full length (a return >= n means the copy was cut short).  Host-side only:
  * the names are recorded where each launch is checked. */

@@ -138,6 +138,7 @@ SIGNATURES = {
     "pp_sparse_ce_lowres_fwd_bwd": (_int, [_p, _i64] + [_int] * 7 + [_p, _int, _p, _p, _p, _p, _i64, _p, _sz, _p]),
     "pp_confusion_matrix_update": (_int, [_p, _int, _int, _i64, _i64, _i64, _p, _p, _p]),
     "pp_predict_lowres": (_int, [_p] + [_i64] * 7 + [_int, _i64, _i64, _p, _int, _p, _p, _p]),
+    "pp_confusion_matrix_from_labels": (_int, [_p, _p, _int, _i64, _int, _p, _p]),
     "pp_vis_lowres_workspace_bytes": (_sz, [_i64] * 3),
     "pp_vis_lowres": (_int, [_p] + [_i64] * 7 + [_int, _i64, _i64, _p, _i64, _i64, _i64, _p, _int, _p, _p, _p, _p, _p, _sz, _p]),
     "pp_adam_step_flat": (_int, [_p, _p, _p, _p, _i64, _i64, _f, _f, _f, _f, _f, _f, _i64, _f, _p, _p]),
@@ -178,6 +179,7 @@ KNOB_SIGNATURES = {
     "pp_debug_set_conv_thresholds": (None, [_int]),
     "pp_debug_conv_plan": (None, [_i64, _int, _int, _int, _p]),
     "pp_debug_set_conv_variant": (None, [_int]),
+    "pp_debug_set_ce_stream": (None, [_int]),
     "pp_debug_set_conv_rows": (None, [_int]),
     "pp_debug_set_conv_bn_fuse": (None, [_int]),
     "pp_debug_set_x3": (None, [_int]),

@@ -2105,6 +2105,131 @@ __global__ __launch_bounds__(kT) void ce_lowres_bwd_kernel(const float* low, int
         if (EXACT || c < C) dst[c] = acc[c];
 }
 
+// ---- streamed forms: any class count ------------------------------------------------------------------------------------
+// The register kernels above hold the interpolated class vector (and, in the backward, one accumulator per class) in VGPRs and
+// stop at 64 classes.  Heads wider than that (Mapillary 66 / 124, ADE20K 150, COCO-Stuff 171; the reference takes n_classes from
+// the data set configuration) walk the four taps' class vectors - contiguous in the channels-last tensor - from memory instead:
+// pass 1 the maximum, pass 2 the sum of exponentials (the same 4*C floats again, served by the cache), in the register kernels'
+// operation order (ascending classes, one running sum), so that on a narrow head the two forms agree to the last bit.
+struct CeTaps {
+    const float *p00, *p01, *p10, *p11;
+    float h0, h1, w0, w1;
+    __device__ __forceinline__ float at(int c) const { return bilerp(h0, h1, w0, w1, p00[c], p01[c], p10[c], p11[c]); }
+};
+
+__device__ __forceinline__ CeTaps ce_taps(const float* base, int64_t ldx, int w, const Lerp& lh, const Lerp& lw)
+{
+    CeTaps t;
+    t.p00 = base + ((int64_t)lh.i0 * w + lw.i0) * ldx;
+    t.p01 = base + ((int64_t)lh.i0 * w + lw.i1) * ldx;
+    t.p10 = base + ((int64_t)lh.i1 * w + lw.i0) * ldx;
+    t.p11 = base + ((int64_t)lh.i1 * w + lw.i1) * ldx;
+    t.h0 = lh.l0; t.h1 = lh.l1; t.w0 = lw.l0; t.w1 = lw.l1;
+    return t;
+}
+
+// m = max_c x_c, S = sum_c exp(x_c - m), xt = x_tg (0 when tg is no class) of one interpolated pixel
+__device__ __forceinline__ void ce_stream_stats(const CeTaps& t, int C, int64_t tg, float& m, float& S, float& xt)
+{
+    m = t.at(0);
+#pragma unroll 8
+    for (int c = 1; c < C; ++c) m = fmaxf(m, t.at(c));
+    S = 0.0f;
+    xt = 0.0f;
+#pragma unroll 8
+    for (int c = 0; c < C; ++c) {
+        const float x = t.at(c);
+        S += expf(x - m);
+        xt = (c == tg) ? x : xt;
+    }
+}
+
+__global__ __launch_bounds__(kT) void ce_lowres_stream_partial_kernel(const float* low, int64_t ldx, int B, int C, int h, int w, int H,
+                                                                     int W, float sh, float sw, int align, const int64_t* target,
+                                                                     int ignore_index, float* part /*[nblk][2]*/)
+{
+    __shared__ float shm[2][kT];
+    float ls = 0.0f, cnt = 0.0f;
+    const int64_t HW = (int64_t)H * W, total = (int64_t)B * HW;
+    for (int64_t e = (int64_t)blockIdx.x * kT + threadIdx.x; e < total; e += (int64_t)gridDim.x * kT) {
+        const int64_t tg = target[e];
+        if (tg == ignore_index) continue;
+        const int64_t b = e / HW, pix = e - b * HW;
+        const int Y = (int)(pix / W), X = (int)(pix - (int64_t)Y * W);
+        const CeTaps t = ce_taps(low + b * h * w * ldx, ldx, w, lerp_src(Y, h, sh, align), lerp_src(X, w, sw, align));
+        float m, S, xt;
+        ce_stream_stats(t, C, tg, m, S, xt);
+        ls += (m + logf(S)) - xt;
+        cnt += 1.0f;
+    }
+    shm[0][threadIdx.x] = ls;
+    shm[1][threadIdx.x] = cnt;
+    __syncthreads();
+    for (int s = kT / 2; s > 0; s >>= 1) {
+        if (threadIdx.x < s) {
+            shm[0][threadIdx.x] += shm[0][threadIdx.x + s];
+            shm[1][threadIdx.x] += shm[1][threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { part[blockIdx.x * 2] = shm[0][0]; part[blockIdx.x * 2 + 1] = shm[1][0]; }
+}
+
+// One thread per (low-resolution pixel, chunk of kCeChunk classes): blockIdx.y is the chunk, so a wave's lanes are neighbouring
+// pixels of one chunk and share their taps.  The thread walks ce_lowres_bwd_kernel's window in its order; for every labelled
+// output pixel it recomputes (max, 1/sum) over ALL classes - labelled pixels are rare, and a stash would cost a workspace sized
+// by the label map - and adds its chunk's  weight * (softmax - onehot).  Fixed order, no atomics; dlow fully written.
+constexpr int kCeChunk = 64;
+__global__ __launch_bounds__(kT) void ce_lowres_stream_bwd_kernel(const float* low, int64_t ldx, int B, int C, int h, int w, int H,
+                                                                 int W, float sh, float sw, int align, const int64_t* target,
+                                                                 int ignore_index, const float* count, const float* grad_out,
+                                                                 float* dlow, int64_t lddx)
+{
+    const int64_t total = (int64_t)B * h * w;
+    const int64_t e = (int64_t)blockIdx.x * kT + threadIdx.x;
+    if (e >= total) return;
+    const int cb = (int)blockIdx.y * kCeChunk;            // first class of this thread's chunk; cb < C by the grid
+    const int nc = C - cb < kCeChunk ? C - cb : kCeChunk;
+    const int c0 = (int)(e % w);
+    const int64_t t = e / w;
+    const int r0 = (int)(t % h);
+    const int b = (int)(t / h);
+    const float gs = (grad_out ? *grad_out : 1.0f) / *count;
+    float acc[kCeChunk];
+#pragma unroll
+    for (int j = 0; j < kCeChunk; ++j) acc[j] = 0.0f;
+    int ylo, yhi, xlo, xhi;
+    out_window(r0, h, H, sh, align, ylo, yhi);
+    out_window(c0, w, W, sw, align, xlo, xhi);
+    const float* base = low + (int64_t)b * h * w * ldx;
+    const int64_t* tb = target + (int64_t)b * H * W;
+    for (int Y = ylo; Y <= yhi; ++Y) {
+        const Lerp lh = lerp_src(Y, h, sh, align);
+        const float wh = (lh.i0 == r0 ? lh.l0 : 0.0f) + (lh.i1 == r0 ? lh.l1 : 0.0f);
+        if (lh.i0 != r0 && lh.i1 != r0) continue;
+        const int64_t* trow = tb + (int64_t)Y * W;
+        for (int X = xlo; X <= xhi; ++X) {
+            const int64_t tg = trow[X];
+            if (tg == ignore_index) continue;
+            const Lerp lw = lerp_src(X, w, sw, align);
+            if (lw.i0 != c0 && lw.i1 != c0) continue;
+            const float ww = (lw.i0 == c0 ? lw.l0 : 0.0f) + (lw.i1 == c0 ? lw.l1 : 0.0f);
+            const CeTaps tp = ce_taps(base, ldx, w, lh, lw);
+            float m, S, xt;
+            ce_stream_stats(tp, C, tg, m, S, xt);
+            const float inv = 1.0f / S, wgt = wh * ww;
+            const int64_t jt = tg - cb;                    // the target's place in this chunk (outside [0, nc): not in it)
+#pragma unroll
+            for (int j = 0; j < kCeChunk; ++j)
+                if (j < nc) acc[j] = fmaf(wgt, gs * (expf(tp.at(cb + j) - m) * inv - ((int64_t)j == jt ? 1.0f : 0.0f)), acc[j]);
+        }
+    }
+    float* dst = dlow + e * lddx + cb;
+#pragma unroll
+    for (int j = 0; j < kCeChunk; ++j)
+        if (j < nc) dst[j] = acc[j];
+}
+
 // ================================================================================================
 // Adam on flat buffers, torch.optim.Adam semantics (L2 weight decay, bias correction), two lr segments
 // (utils/utils.py:125-141: backbone/encoder at lr/10).
@@ -2205,6 +2330,7 @@ __global__ __launch_bounds__(kT) void nhwc_to_nchw_kernel(const float* x, int64_
     }
 }
 
+static int g_ce_stream = 0;   // test build (pp_debug_set_ce_stream): the streamed low-resolution loss kernels on heads of <= 64 classes too
 static int g_bil_sep = 1;   // separable bilinear backward for >= x3 up-sampling (bit 8 of pp_debug_set_dw_variant switches it off)
 static int g_dw_wgrad_x4 = 1, g_dw_wgrad_x4_blocks = 256;   // four-pixel items for the stride-1 depthwise weight gradient
 static int g_dw_wgrad_cq_blk = 0, g_dw_wgrad_passes = 0;      // column-block width / least rows per thread (pp_debug_set_dw_variant bits 13-17); 0 = by map size
@@ -2254,6 +2380,9 @@ void pp_debug_set_bn_bytes_per_block(int bytes)
     g_bn_bytes_per_block = bytes > 0 ? bytes : 0;
     g_bn_row_cache = bytes == -1 ? 0 : 1;          // -1: the register-cached variants off (A/B)
 }
+#endif
+#ifdef PP_DEBUG_KNOBS
+void pp_debug_set_ce_stream(int on) { g_ce_stream = on ? 1 : 0; }
 #endif
 static thread_local unsigned long long* g_bn_probe = nullptr;
 #ifdef PP_DEBUG_KNOBS
@@ -3079,7 +3208,6 @@ int pp_sparse_ce_lowres_fwd_bwd(const float* low, int64_t ldx, int B, int C, int
     if (B < 1 || C < 1 || h < 1 || w < 1 || H < 1 || W < 1 || ldx < C || (dlow && lddx < C))
         return fail(PP_ERR_BAD_ARG, "sparse_ce_lowres: bad shape B=%d C=%d %dx%d -> %dx%d ldx=%lld lddx=%lld", B, C, h, w, H, W,
                     (long long)ldx, (long long)lddx);
-    if (C > 64) return fail(PP_ERR_UNSUPPORTED, "sparse_ce_lowres: C=%d > 64", C);
     if (!workspace || ws_bytes < pp_sparse_ce_lowres_workspace_bytes()) return fail(PP_ERR_WORKSPACE, "sparse_ce_lowres: workspace");
     hipStream_t st = as_stream(stream);
     float sh, sw;
@@ -3103,6 +3231,21 @@ int pp_sparse_ce_lowres_fwd_bwd(const float* low, int64_t ldx, int B, int C, int
             if (int rc = check_launch("ce_lowres_bwd_kernel")) return rc;                                                      \
         }                                                                                                                      \
     } while (0)
+    if (C > 64 || g_ce_stream) {   // any class count: the class vector is walked from memory (the workspace holds the block partials only)
+        hipLaunchKernelGGL(ce_lowres_stream_partial_kernel, dim3(nblk), dim3(kT), 0, st, low, ldx, B, C, h, w, H, W, sh, sw, al, target,
+                           ignore_index, part);
+        if (int rc = check_launch("ce_lowres_stream_partial_kernel")) return rc;
+        hipLaunchKernelGGL(ce_finalize_wave_kernel, dim3(1), dim3(64), 0, st, part, nblk, loss, count);
+        if (int rc = check_launch("ce_finalize_wave_kernel")) return rc;
+        if (dlow) {
+            const unsigned chunks = (unsigned)cdiv(C, kCeChunk);
+            if (chunks > 65535u) return fail(PP_ERR_UNSUPPORTED, "sparse_ce_lowres: C=%d", C);
+            hipLaunchKernelGGL(ce_lowres_stream_bwd_kernel, dim3(gb, chunks), dim3(kT), 0, st, low, ldx, B, C, h, w, H, W, sh, sw, al,
+                               target, ignore_index, count, grad_out, dlow, lddx);
+            if (int rc = check_launch("ce_lowres_stream_bwd_kernel")) return rc;
+        }
+        return PP_OK;
+    }
     switch (C) {
         case 11: PP_CE_LOW(11, true); break;
         case 19: PP_CE_LOW(19, true); break;

@@ -134,6 +134,7 @@ const Entry kEntries[] = {
     PP_PLAN_ENTRY(pp_sparse_ce_fwd_bwd),
     PP_PLAN_ENTRY(pp_sparse_ce_lowres_fwd_bwd),
     PP_PLAN_ENTRY(pp_confusion_matrix_update),
+    PP_PLAN_ENTRY(pp_confusion_matrix_from_labels),
     PP_PLAN_ENTRY(pp_predict_lowres),
     PP_PLAN_ENTRY(pp_vis_lowres),
     PP_PLAN_ENTRY(pp_adam_step_flat),

@@ -1840,7 +1840,8 @@ def cross_entropy_lowres(low: torch.Tensor, size, target: torch.Tensor, ignore_i
                          want_grad: bool = True, sparse: bool = True):
     """F.cross_entropy(F.interpolate(low, size, 'bilinear', align_corners), target, ignore_index) and its gradient w.r.t.
     `low`, without the full-size logits (deeplab.py:55-56 + model.py:116).  low [B,h,w,C] channels-last (the classifier
-    output), target [B,H,W] int64 -> (loss [1], dlow [B,h,w,C] | None)."""
+    output), target [B,H,W] int64 -> (loss [1], dlow [B,h,w,C] | None).  Any class count: up to 64 classes the kernels hold the
+    class vector in registers, wider heads stream it from memory (csrc/nn_ops.hip, ce_lowres_stream_*)."""
     assert low.is_cuda and low.dtype == torch.float32 and low.dim() == 4 and low.stride(3) == 1
     B, h, w, C = low.shape
     assert low.stride(1) == w * low.stride(2) and low.stride(0) == h * low.stride(1)

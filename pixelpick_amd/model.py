@@ -199,7 +199,7 @@ class Model:
         local_it = -1
         from . import trainer as _tr
         keep = "low" if (self._metrics_lowres and _tr.SPARSE_LOWRES_CE and getattr(model, "LOWRES_LOGITS", False)
-                         and self.n_classes <= 104) else True
+                         and self.n_classes <= 256) else True
         x = y_shown = None
         for it, dict_data in enumerate(loader):
             if skip:
@@ -263,7 +263,13 @@ class Model:
                 self.vis.from_lowres(trainer.last_low, trainer.last_low_size, x, y_shown, self._picture_path(epoch, "train"),
                                      align_corners=trainer.last_low_align)
             else:
-                self._picture_from_logits(trainer.last_logits[:1], x[0], y_shown[0], self._picture_path(epoch, "train"))
+                logits = trainer.last_logits
+                if logits is None:          # keep_logits="low" on a head wider than the picture kernels take: interpolate the shown image
+                    from . import engine as E
+                    al = trainer.last_low_align
+                    logits = E.bilinear(E.Tape(False), E.Var(trainer.last_low[:1]), trainer.last_low_size, al,
+                                        0.0 if al else float(getattr(model, "LOWRES_SCALE_FACTOR", 0.0)), out_nchw=True).t
+                self._picture_from_logits(logits[:1], x[0], y_shown[0], self._picture_path(epoch, "train"))
         trainer.sync_buffers()
         self._all_reduce_scores()
         scores = self.running_score.get_scores()[0]
@@ -341,7 +347,7 @@ class Model:
         # launches), so consecutive images of equal size are forwarded `val_batch_size` at a time (default 8).
         vbs = int(getattr(self.args, "val_batch_size", 8))
         pend_x, pend_y = [], []
-        lowres = (self._metrics_lowres and callable(getattr(model, "forward_lowres", None)) and self.n_classes <= 104
+        lowres = (self._metrics_lowres and callable(getattr(model, "forward_lowres", None)) and self.n_classes <= 256
                   and (getattr(model, "LOWRES_EXACT", False) or self._metrics_lowres_forced))
 
         shown = []               # what the picture needs of the last forwarded image (args.visualise)

@@ -21,7 +21,8 @@ def predict_lowres(low: torch.Tensor, size, crop=None, align_corners: bool = Tru
     """low [B,h,w,C] f32 channels-last on the GPU (the classifier output as the engine keeps it); size = (H, W) interpolated
     to; crop = (Hc, Wc) <= size, the top-left region kept (VOC).  target [B,Hc,Wc] uint8 or int64 on the same device and
     hist int64 [C,C] (ACCUMULATED into: hist[t, argmax] += 1 where 0 <= t < C) go together; C <= 104 with hist, <= 256 with
-    want_pred.  Returns (pred uint8 [B,Hc,Wc] | None, hist | None); enqueued on the current stream, no sync."""
+    want_pred (a wider head's histogram: take the label map and hand it to RunningScore.update_from_labels /
+    pp_confusion_matrix_from_labels, as RunningScore.update_from_lowres does).  Returns (pred uint8 [B,Hc,Wc] | None, hist | None); enqueued on the current stream, no sync."""
     B, h, w, C, ldx, H, W, Hc, Wc = _lowres_geom(low, size, crop)
     dev = low.device
     if not want_pred and hist is None:

@@ -15,6 +15,7 @@
 
 #include "pp_common.h"
 #include "acq_score.h"
+#include "lowres_tile.h"
 #include <type_traits>
 
 namespace pp {
@@ -613,9 +614,9 @@ __global__ __launch_bounds__(kBlock, (CMAX > 19 ? 2 : 3)) void acq_nhwc_dma_kern
 // Replaces  deeplab.py:55-56  F.interpolate(pred, size=inputs.shape[2:], mode='bilinear', align_corners=True)
 //        +  query.py:190      softmax(model(x)["pred"][:, :, :h, :w])  + score + exclusion + top-k
 // without ever writing the full-resolution logits (10 MB per 256x512x19 image written and read back; the algorithmic
-// input drops 16x to the 64x128x19 classifier output).  A block owns a 64-column x 4*PPT-row tile of OUTPUT pixels,
-// stages the low-resolution patch the tile interpolates from in LDS ((4*PPT*s+2) x (64*s+2) pixels, 13.7 KB at s = 1/4),
-// and every lane interpolates its pixels' class vectors from LDS with bilerp() - the same bits pp_bilinear_fwd writes -
+// input drops 16x to the 64x128x19 classifier output).  A block owns a 64-column x 4*PPT-row LowresTile (lowres_tile.h) of
+// OUTPUT pixels, stages the low-resolution patch the tile interpolates from in LDS ((4*PPT*s+2) x (64*s+2) pixels, 13.7 KB at
+// s = 1/4), and every lane interpolates its pixels' class vectors from the tile's taps - the same bits pp_bilinear_fwd writes -
 // then scores them like acq_kernel.  Wave w of the tile owns PPT consecutive rows, so the row weights are wave-uniform.
 struct LowresParams {
     const float* low;    // [B,h,w,ldx] channels-last, C valid channels
@@ -632,6 +633,28 @@ struct LowresParams {
     float qscale = 0.0f;
 };
 
+// The per-pixel selection tail of the low-resolution scorers: exclusion fill, map store, the score's bin (qbins: the block's LDS
+// histogram, or null) and the candidate key (larger = selected earlier; ties: the lower flat index).
+__device__ __forceinline__ void lowres_emit_key(float sc, int64_t pix, bool largest, float fill, const uint8_t* excl, float* omap,
+                                                uint32_t* qbins, float qscale, uint32_t& kh, uint32_t& kl)
+{
+    if (excl && excl[pix]) sc = fill;
+    if (omap) omap[pix] = sc;
+    if (qbins) atomicAdd(&qbins[qbin(sc, largest, qscale)], 1u);
+    kh = order_key(sc, largest);
+    kl = 0xFFFFFFFFu - (uint32_t)pix;
+}
+
+// the block's bins -> the image's histogram Hg (non-zero bins only)
+__device__ __forceinline__ void lowres_hist_flush(const uint32_t* qbins, uint32_t* Hg)
+{
+    __syncthreads();
+    for (int d = threadIdx.x; d < kQBins; d += kBlock) {
+        const uint32_t c = qbins[d];
+        if (c) atomicAdd(&Hg[d], c);
+    }
+}
+
 template <int CMAX, bool EXACT, int PPT, bool LDS, int MATH, int STRAT = -1>
 __global__ __launch_bounds__(kBlock, 2) void acq_lowres_kernel(LowresParams p)
 {
@@ -639,7 +662,6 @@ __global__ __launch_bounds__(kBlock, 2) void acq_lowres_kernel(LowresParams p)
     __shared__ uint64_t s_surv[kBlock / kWave][kSurvCap];
     __shared__ uint32_t s_cnt[kBlock / kWave];
     __shared__ uint64_t s_top[(kBlock / kWave) * kSmallKMax];
-    constexpr int TR = (kBlock / kWave) * PPT, TC = kWave;
     const int tiles = p.tiles_x * p.tiles_y;
     const int img = blockIdx.x / tiles;
     const int t = blockIdx.x - img * tiles;
@@ -647,77 +669,47 @@ __global__ __launch_bounds__(kBlock, 2) void acq_lowres_kernel(LowresParams p)
     const int tid = threadIdx.x, lane = tid & (kWave - 1);
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     // large-k selection: the block counts its scores into the image's histogram (as acq_kernel<..., HIST>; bins in the survivor lists)
-    uint32_t* qbins = reinterpret_cast<uint32_t*>(&s_surv[0][0]);
-    const bool hist = p.qhist != nullptr;
-    if (hist) {
+    uint32_t* qbins = p.qhist ? reinterpret_cast<uint32_t*>(&s_surv[0][0]) : nullptr;
+    if (qbins) {
         for (int i = tid; i < kQBins; i += kBlock) qbins[i] = 0u;
         __syncthreads();
     }
     const int C = EXACT ? CMAX : p.C;
-    const int CP = C | 1;                     // odd pixel pitch: lanes 4 columns apart hit different banks
     const bool largest = p.strategy != PP_ACQ_MARGIN;
     const float fill = largest ? 0.0f : 1.0f;
     const int64_t N = (int64_t)p.Hc * p.Wc;
-    const int X0 = tx * TC, Y0 = ty * TR;
-    const int X1 = min(X0 + TC - 1, p.Wc - 1), Y1 = min(Y0 + TR - 1, p.Hc - 1);
-    const int c_lo = lerp_src(X0, p.w, p.sw, p.align).i0, c_hi = lerp_src(X1, p.w, p.sw, p.align).i1;
-    const int r_lo = lerp_src(Y0, p.h, p.sh, p.align).i0, r_hi = lerp_src(Y1, p.h, p.sh, p.align).i1;
-    const int pw = c_hi - c_lo + 1, ph = r_hi - r_lo + 1;
+    LowresTile<LDS> tile(p, C, tx, ty, (kBlock / kWave) * PPT, kBlock);
     const float* base = p.low + (int64_t)img * p.h * p.w * p.ldx;
     if constexpr (LDS) {
-        if (ph * pw * CP > p.patch_cap) __builtin_trap();   // host sizing bug: never silently read past the patch
-        const int n = ph * pw * C;
-        for (int e = tid; e < n; e += kBlock) {
-            const int pc = e / C, ch = e - pc * C;
-            const int r = pc / pw, c = pc - r * pw;
-            s_patch[pc * CP + ch] = base[((int64_t)(r_lo + r) * p.w + c_lo + c) * p.ldx + ch];
-        }
+        tile.stage(p, s_patch, base);
         __syncthreads();
     }
+    tile.set_lane(p, lane);
     const uint8_t* excl = p.exclude ? p.exclude + (int64_t)img * N : nullptr;
     float* omap = p.out_map ? p.out_map + (int64_t)img * N : nullptr;
-    const int X = X0 + lane;
-    const bool xin = X < p.Wc;
-    const Lerp lw = lerp_src(xin ? X : X1, p.w, p.sw, p.align);
-    const int64_t pitch = LDS ? (int64_t)CP : p.ldx;
-    const int64_t o0 = (int64_t)(LDS ? lw.i0 - c_lo : lw.i0) * pitch, o1 = (int64_t)(LDS ? lw.i1 - c_lo : lw.i1) * pitch;
     const float* src = LDS ? s_patch : base;
-    const int64_t row_pitch = (LDS ? pw : p.w) * pitch;
 
     uint32_t kh[PPT], kl[PPT];
 #pragma unroll
     for (int j = 0; j < PPT; ++j) {
-        const int Y = Y0 + wv * PPT + j;
-        if (Y < p.Hc && xin) {
-            const Lerp lh = lerp_src(Y, p.h, p.sh, p.align);
-            const float* r0 = src + (int64_t)(LDS ? lh.i0 - r_lo : lh.i0) * row_pitch;
-            const float* r1 = src + (int64_t)(LDS ? lh.i1 - r_lo : lh.i1) * row_pitch;
+        const int Y = tile.Y0 + wv * PPT + j;
+        if (Y < p.Hc && tile.xin) {
             float x[CMAX];
+            const auto tp = tile.taps(src, tile.row(p, Y));
 #pragma unroll
             for (int c = 0; c < CMAX; ++c)
-                if (EXACT || c < C)
-                    x[c] = bilerp(lh.l0, lh.l1, lw.l0, lw.l1, r0[o0 + c], r0[o1 + c], r1[o0 + c], r1[o1 + c]);
+                if (EXACT || c < C) x[c] = tp.at(c);
             float sc;
             if constexpr (MATH == 0) sc = pixel_score_fast<CMAX, EXACT, STRAT>(x, p.C, p.strategy);
             else sc = pixel_score<CMAX, EXACT>(x, p.C, p.strategy, 0);
-            const int64_t pix = (int64_t)Y * p.Wc + X;
-            if (excl && excl[pix]) sc = fill;
-            if (omap) omap[pix] = sc;
-            if (hist) atomicAdd(&qbins[qbin(sc, largest, p.qscale)], 1u);
-            kh[j] = order_key(sc, largest);
-            kl[j] = 0xFFFFFFFFu - (uint32_t)pix;
+            lowres_emit_key(sc, (int64_t)Y * p.Wc + tile.X, largest, fill, excl, omap, qbins, p.qscale, kh[j], kl[j]);
         } else {
             kh[j] = 0u; kl[j] = 0u;
         }
         __builtin_amdgcn_sched_barrier(0);   // one pixel's class vector live at a time
     }
-    if (hist) {
-        __syncthreads();
-        uint32_t* Hg = p.qhist + (int64_t)img * kQBins;
-        for (int d = tid; d < kQBins; d += kBlock) {
-            const uint32_t c = qbins[d];
-            if (c) atomicAdd(&Hg[d], c);
-        }
+    if (qbins) {
+        lowres_hist_flush(qbins, p.qhist + (int64_t)img * kQBins);
         return;
     }
     if (p.cand)
@@ -737,25 +729,22 @@ __global__ __launch_bounds__(kBlock) void acq_lowres_at_kernel(const float* low,
     const int pix = pix_idx[i], Y = pix / Wc, X = pix - Y * Wc;
     const Lerp lh = lerp_src(Y, h, sh, align), lw = lerp_src(X, w, sw, align);
     const float* base = low + (int64_t)img_idx[i] * h * w * ldx;
-    const float* p00 = base + ((int64_t)lh.i0 * w + lw.i0) * ldx;
-    const float* p01 = base + ((int64_t)lh.i0 * w + lw.i1) * ldx;
-    const float* p10 = base + ((int64_t)lh.i1 * w + lw.i0) * ldx;
-    const float* p11 = base + ((int64_t)lh.i1 * w + lw.i1) * ldx;
     float x[CMAX];
+    const auto tp = lowres_taps(base, ldx, w, lh, lw);
 #pragma unroll
     for (int c = 0; c < CMAX; ++c)
-        if (EXACT || c < C) x[c] = bilerp(lh.l0, lh.l1, lw.l0, lw.l1, p00[c], p01[c], p10[c], p11[c]);
+        if (EXACT || c < C) x[c] = tp.at(c);
     out[i] = pixel_score_fast<CMAX, EXACT>(x, C, strategy);
 }
 
 // ---- MC-dropout acquisition from the low-resolution classifier output (query.py:177-187) --------------------------------
 // The mean over T stochastic passes of the strategy's score, without the T full-resolution logit tensors (T x 10 MB per 256x512x19
-// image written by pp_bilinear_fwd and read back by softmax_sum_kernel): acq_lowres_kernel's tile, looped over the passes.  `low`
-// is image-major, passes t = 0..T-1 of image b are entries b*T + t.  Per pass the block stages that pass's source patch in LDS
-// (same geometry and odd pixel pitch), every lane interpolates its pixels' class vectors with bilerp() and adds mc_pass_score()
-// - softmax_sum_kernel's arithmetic - to a per-pixel register accumulator; scale * sum, the exclusion fill and the selection
-// epilogues of acq_lowres_kernel follow.  The HOST guarantees that the patch fits p.patch_cap (make_lowres_plan's bound on the
-// patch of any tile); a shape whose patch does not fit runs the LDS = false form, which reads the four neighbours from memory.
+// image written by pp_bilinear_fwd and read back by softmax_sum_kernel): one LowresTile, its patch staged once per pass.  `low`
+// is image-major, passes t = 0..T-1 of image b are entries b*T + t.  Per pass every lane interpolates its pixels' class vectors
+// from the tile's taps and adds mc_pass_score() - softmax_sum_kernel's arithmetic - to a per-pixel register accumulator;
+// scale * sum and the selection tail (lowres_emit_key) follow.  A shape whose patch does not fit the LDS a block may ask for
+// (make_lowres_plan) runs the LDS = false form, which reads the four neighbours from memory; that the patch fits patch_cap is the
+// HOST's guarantee here (lowres_patch_floats()): the one tile kernel that stages without the frame's capacity trap.
 struct LowresMcParams {
     LowresParams g;      // low: [B*T,h,w,ldx]
     int T;
@@ -770,37 +759,25 @@ __global__ __launch_bounds__(kBlock, 2) void acq_lowres_mc_kernel(LowresMcParams
     __shared__ uint32_t s_cnt[kBlock / kWave];
     __shared__ uint64_t s_top[(kBlock / kWave) * kSmallKMax];
     const LowresParams& p = q.g;
-    constexpr int TR = (kBlock / kWave) * PPT, TC = kWave;
     const int tiles = p.tiles_x * p.tiles_y;
     const int img = blockIdx.x / tiles;
     const int t = blockIdx.x - img * tiles;
     const int ty = t / p.tiles_x, tx = t - ty * p.tiles_x;
     const int tid = threadIdx.x, lane = tid & (kWave - 1);
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    uint32_t* qbins = reinterpret_cast<uint32_t*>(&s_surv[0][0]);
-    const bool hist = p.qhist != nullptr;
-    if (hist) {
+    uint32_t* qbins = p.qhist ? reinterpret_cast<uint32_t*>(&s_surv[0][0]) : nullptr;
+    if (qbins) {
         for (int i = tid; i < kQBins; i += kBlock) qbins[i] = 0u;
         __syncthreads();
     }
     const int C = EXACT ? CMAX : p.C;
-    const int CP = C | 1;
     const bool largest = p.strategy != PP_ACQ_MARGIN;
     const float fill = largest ? 0.0f : 1.0f;
     const int64_t N = (int64_t)p.Hc * p.Wc;
-    const int X0 = tx * TC, Y0 = ty * TR;
-    const int X1 = min(X0 + TC - 1, p.Wc - 1), Y1 = min(Y0 + TR - 1, p.Hc - 1);
-    const int c_lo = lerp_src(X0, p.w, p.sw, p.align).i0, c_hi = lerp_src(X1, p.w, p.sw, p.align).i1;
-    const int r_lo = lerp_src(Y0, p.h, p.sh, p.align).i0, r_hi = lerp_src(Y1, p.h, p.sh, p.align).i1;
-    const int pw = c_hi - c_lo + 1, ph = r_hi - r_lo + 1;
+    LowresTile<LDS> tile(p, C, tx, ty, (kBlock / kWave) * PPT, kBlock);
+    tile.set_lane(p, lane);
     const int64_t pass_stride = (int64_t)p.h * p.w * p.ldx;
     const float* img_base = p.low + (int64_t)img * q.T * pass_stride;
-    const int X = X0 + lane;
-    const bool xin = X < p.Wc;
-    const Lerp lw = lerp_src(xin ? X : X1, p.w, p.sw, p.align);
-    const int64_t pitch = LDS ? (int64_t)CP : p.ldx;
-    const int64_t o0 = (int64_t)(LDS ? lw.i0 - c_lo : lw.i0) * pitch, o1 = (int64_t)(LDS ? lw.i1 - c_lo : lw.i1) * pitch;
-    const int64_t row_pitch = (LDS ? pw : p.w) * pitch;
 
     float uc[PPT];
 #pragma unroll
@@ -809,27 +786,26 @@ __global__ __launch_bounds__(kBlock, 2) void acq_lowres_mc_kernel(LowresMcParams
         const float* base = img_base + (int64_t)ps * pass_stride;
         if constexpr (LDS) {
             if (ps) __syncthreads();          // every wave has finished reading the previous pass's patch
-            const int n = ph * pw * C;
+            // tile.stage() spelled out, without its capacity trap: in this kernel the trap costs the generic forms 36 B of scratch and
+            // the call <21, 4 rows, entropy> a wave per SIMD (profiles/lowres_tile_resources.txt)
+            const int n = tile.ph * tile.pw * C;
             for (int e = tid; e < n; e += kBlock) {
                 const int pc = e / C, ch = e - pc * C;
-                const int r = pc / pw, c = pc - r * pw;
-                s_patch[pc * CP + ch] = base[((int64_t)(r_lo + r) * p.w + c_lo + c) * p.ldx + ch];
+                const int r = pc / tile.pw, c = pc - r * tile.pw;
+                s_patch[pc * (C | 1) + ch] = base[((int64_t)(tile.r_lo + r) * p.w + tile.c_lo + c) * p.ldx + ch];
             }
             __syncthreads();
         }
         const float* src = LDS ? s_patch : base;
 #pragma unroll
         for (int j = 0; j < PPT; ++j) {
-            const int Y = Y0 + wv * PPT + j;
-            if (Y < p.Hc && xin) {
-                const Lerp lh = lerp_src(Y, p.h, p.sh, p.align);
-                const float* r0 = src + (int64_t)(LDS ? lh.i0 - r_lo : lh.i0) * row_pitch;
-                const float* r1 = src + (int64_t)(LDS ? lh.i1 - r_lo : lh.i1) * row_pitch;
+            const int Y = tile.Y0 + wv * PPT + j;
+            if (Y < p.Hc && tile.xin) {
                 float x[CMAX];
+                const auto tp = tile.taps(src, tile.row(p, Y));
 #pragma unroll
                 for (int c = 0; c < CMAX; ++c)
-                    if (EXACT || c < C)
-                        x[c] = bilerp(lh.l0, lh.l1, lw.l0, lw.l1, r0[o0 + c], r0[o1 + c], r1[o0 + c], r1[o1 + c]);
+                    if (EXACT || c < C) x[c] = tp.at(c);
                 uc[j] += mc_pass_score<STRAT, CMAX, EXACT>([&](int c) { return x[c]; }, C, p.strategy, [](int, float) {});
             }
             __builtin_amdgcn_sched_barrier(0);   // one pixel's class vector live at a time
@@ -841,26 +817,15 @@ __global__ __launch_bounds__(kBlock, 2) void acq_lowres_mc_kernel(LowresMcParams
     uint32_t kh[PPT], kl[PPT];
 #pragma unroll
     for (int j = 0; j < PPT; ++j) {
-        const int Y = Y0 + wv * PPT + j;
-        if (Y < p.Hc && xin) {
-            float sc = q.scale * uc[j];
-            const int64_t pix = (int64_t)Y * p.Wc + X;
-            if (excl && excl[pix]) sc = fill;
-            if (omap) omap[pix] = sc;
-            if (hist) atomicAdd(&qbins[qbin(sc, largest, p.qscale)], 1u);
-            kh[j] = order_key(sc, largest);
-            kl[j] = 0xFFFFFFFFu - (uint32_t)pix;
+        const int Y = tile.Y0 + wv * PPT + j;
+        if (Y < p.Hc && tile.xin) {
+            lowres_emit_key(q.scale * uc[j], (int64_t)Y * p.Wc + tile.X, largest, fill, excl, omap, qbins, p.qscale, kh[j], kl[j]);
         } else {
             kh[j] = 0u; kl[j] = 0u;
         }
     }
-    if (hist) {
-        __syncthreads();
-        uint32_t* Hg = p.qhist + (int64_t)img * kQBins;
-        for (int d = tid; d < kQBins; d += kBlock) {
-            const uint32_t c = qbins[d];
-            if (c) atomicAdd(&Hg[d], c);
-        }
+    if (qbins) {
+        lowres_hist_flush(qbins, p.qhist + (int64_t)img * kQBins);
         return;
     }
     if (p.cand)
@@ -881,17 +846,15 @@ __global__ __launch_bounds__(kBlock) void acq_lowres_mc_at_kernel(const float* l
     const Lerp lh = lerp_src(Y, h, sh, align), lw = lerp_src(X, w, sw, align);
     const int64_t pass_stride = (int64_t)h * w * ldx;
     const float* base = low + (int64_t)img_idx[i] * T * pass_stride;
-    const int64_t a00 = ((int64_t)lh.i0 * w + lw.i0) * ldx, a01 = ((int64_t)lh.i0 * w + lw.i1) * ldx;
-    const int64_t a10 = ((int64_t)lh.i1 * w + lw.i0) * ldx, a11 = ((int64_t)lh.i1 * w + lw.i1) * ldx;
     float acc[CMAX];
 #pragma unroll
     for (int c = 0; c < CMAX; ++c) acc[c] = 0.0f;
     for (int t = 0; t < T; ++t) {
-        const float* b = base + (int64_t)t * pass_stride;
         float x[CMAX];
+        const auto tp = lowres_taps(base + (int64_t)t * pass_stride, ldx, w, lh, lw);
 #pragma unroll
         for (int c = 0; c < CMAX; ++c)
-            if (EXACT || c < C) x[c] = bilerp(lh.l0, lh.l1, lw.l0, lw.l1, b[a00 + c], b[a01 + c], b[a10 + c], b[a11 + c]);
+            if (EXACT || c < C) x[c] = tp.at(c);
         // (STRAT = least-confidence: only the probabilities are wanted here, no logf per pass)
         (void)mc_pass_score<PP_ACQ_LEAST_CONFIDENCE, CMAX, EXACT>([&](int c) { return x[c]; }, C, 0, [&](int c, float pc) { acc[c] += pc; });
     }
@@ -920,7 +883,7 @@ __device__ __forceinline__ float vote_score(int strategy, uint32_t n1, uint32_t 
 }
 __device__ __forceinline__ float vote_fill(int strategy) { return strategy != PP_ACQ_MARGIN ? -1.0f : 2.0f; }
 
-// acq_lowres_mc_kernel's tile, patch staging, bilerp, exclusion, map store and candidate epilogue; per pass a running maximum in
+// acq_lowres_mc_kernel's pass loop over one LowresTile and its selection tail; per pass a running maximum in
 // ascending class order (strict >: the lowest class wins ties) and ONE vote into the pixel's counters - bytes packed four to a
 // 32-bit register, (CMAX+3)/4 words per pixel, bumped by an unrolled compare-and-add (no run-time register index: no scratch).
 // No expf / logf in the pass loop.  The table is staged once per block into the survivor lists' LDS (free until block_emit_topk).
@@ -938,7 +901,6 @@ __global__ __launch_bounds__(kBlock, 2) void acq_lowres_mc_vote_kernel(LowresVot
     __shared__ uint32_t s_cnt[kBlock / kWave];
     __shared__ uint64_t s_top[(kBlock / kWave) * kSmallKMax];
     const LowresParams& p = q.g;
-    constexpr int TR = (kBlock / kWave) * PPT, TC = kWave;
     constexpr int NW = (CMAX + 3) / 4;
     const int tiles = p.tiles_x * p.tiles_y;
     const int img = blockIdx.x / tiles;
@@ -947,25 +909,12 @@ __global__ __launch_bounds__(kBlock, 2) void acq_lowres_mc_vote_kernel(LowresVot
     const int tid = threadIdx.x, lane = tid & (kWave - 1);
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int C = EXACT ? CMAX : p.C;
-    const int CP = C | 1;
     const bool largest = p.strategy != PP_ACQ_MARGIN;
     const int64_t N = (int64_t)p.Hc * p.Wc;
-    const int X0 = tx * TC, Y0 = ty * TR;
-    const int X1 = min(X0 + TC - 1, p.Wc - 1), Y1 = min(Y0 + TR - 1, p.Hc - 1);
-    const int c_lo = lerp_src(X0, p.w, p.sw, p.align).i0, c_hi = lerp_src(X1, p.w, p.sw, p.align).i1;
-    const int r_lo = lerp_src(Y0, p.h, p.sh, p.align).i0, r_hi = lerp_src(Y1, p.h, p.sh, p.align).i1;
-    const int pw = c_hi - c_lo + 1, ph = r_hi - r_lo + 1;
+    LowresTile<LDS> tile(p, C, tx, ty, (kBlock / kWave) * PPT, kBlock);
+    tile.set_lane(p, lane);
     const int64_t pass_stride = (int64_t)p.h * p.w * p.ldx;
     const float* img_base = p.low + (int64_t)img * q.T * pass_stride;
-    const int X = X0 + lane;
-    const bool xin = X < p.Wc;
-    const Lerp lw = lerp_src(xin ? X : X1, p.w, p.sw, p.align);
-    const int64_t pitch = LDS ? (int64_t)CP : p.ldx;
-    const int64_t o0 = (int64_t)(LDS ? lw.i0 - c_lo : lw.i0) * pitch, o1 = (int64_t)(LDS ? lw.i1 - c_lo : lw.i1) * pitch;
-    const int64_t row_pitch = (LDS ? pw : p.w) * pitch;
-    if constexpr (LDS) {
-        if (ph * pw * CP > p.patch_cap) __builtin_trap();   // host sizing bug: never silently read past the patch
-    }
 
     uint32_t cnt[PPT][NW];
 #pragma unroll
@@ -976,28 +925,21 @@ __global__ __launch_bounds__(kBlock, 2) void acq_lowres_mc_vote_kernel(LowresVot
         const float* base = img_base + (int64_t)ps * pass_stride;
         if constexpr (LDS) {
             if (ps) __syncthreads();          // every wave has finished reading the previous pass's patch
-            const int n = ph * pw * C;
-            for (int e = tid; e < n; e += kBlock) {
-                const int pc = e / C, ch = e - pc * C;
-                const int r = pc / pw, c = pc - r * pw;
-                s_patch[pc * CP + ch] = base[((int64_t)(r_lo + r) * p.w + c_lo + c) * p.ldx + ch];
-            }
+            tile.stage(p, s_patch, base);
             __syncthreads();
         }
         const float* src = LDS ? s_patch : base;
 #pragma unroll
         for (int j = 0; j < PPT; ++j) {
-            const int Y = Y0 + wv * PPT + j;
-            if (Y < p.Hc && xin) {
-                const Lerp lh = lerp_src(Y, p.h, p.sh, p.align);
-                const float* r0 = src + (int64_t)(LDS ? lh.i0 - r_lo : lh.i0) * row_pitch;
-                const float* r1 = src + (int64_t)(LDS ? lh.i1 - r_lo : lh.i1) * row_pitch;
-                float best = bilerp(lh.l0, lh.l1, lw.l0, lw.l1, r0[o0], r0[o1], r1[o0], r1[o1]);
+            const int Y = tile.Y0 + wv * PPT + j;
+            if (Y < p.Hc && tile.xin) {
+                const auto tp = tile.taps(src, tile.row(p, Y));
+                float best = tp.at(0);
                 int bi = 0;
 #pragma unroll
                 for (int c = 1; c < CMAX; ++c)
                     if (EXACT || c < C) {
-                        const float v = bilerp(lh.l0, lh.l1, lw.l0, lw.l1, r0[o0 + c], r0[o1 + c], r1[o0 + c], r1[o1 + c]);
+                        const float v = tp.at(c);
                         if (v > best) { best = v; bi = c; }
                     }
                 const uint32_t inc = 1u << ((bi & 3) * 8);
@@ -1019,8 +961,8 @@ __global__ __launch_bounds__(kBlock, 2) void acq_lowres_mc_vote_kernel(LowresVot
     uint32_t kh[PPT], kl[PPT];
 #pragma unroll
     for (int j = 0; j < PPT; ++j) {
-        const int Y = Y0 + wv * PPT + j;
-        if (Y < p.Hc && xin) {
+        const int Y = tile.Y0 + wv * PPT + j;
+        if (Y < p.Hc && tile.xin) {
             uint32_t n1 = 0u, n2 = 0u, eq = 0u;
 #pragma unroll
             for (int c = 0; c < CMAX; ++c) {
@@ -1029,12 +971,8 @@ __global__ __launch_bounds__(kBlock, 2) void acq_lowres_mc_vote_kernel(LowresVot
                 n1 = max(n1, n);
                 if (want_ent) eq += s_tab[n];
             }
-            float sc = vote_score(p.strategy, n1, n2, eq, q.T);
-            const int64_t pix = (int64_t)Y * p.Wc + X;
-            if (excl && excl[pix]) sc = vote_fill(p.strategy);
-            if (omap) omap[pix] = sc;
-            kh[j] = order_key(sc, largest);
-            kl[j] = 0xFFFFFFFFu - (uint32_t)pix;
+            lowres_emit_key(vote_score(p.strategy, n1, n2, eq, q.T), (int64_t)Y * p.Wc + tile.X, largest, vote_fill(p.strategy), excl, omap,
+                            nullptr, 0.0f, kh[j], kl[j]);
         } else {
             kh[j] = 0u; kl[j] = 0u;
         }
@@ -1257,8 +1195,8 @@ __global__ __launch_bounds__(kBlock) void acq_stream_kernel(AcqParams p)
         block_emit_topk<PPT>(kh, kl, p.k, p.cand + ((int64_t)img * p.blocks_per_image + blk) * p.k, p.reduce_mode, s_surv, s_cnt, s_top);
 }
 
-// acq_lowres_kernel's tile geometry (PPT = 4, no LDS patch): every class of a pixel is interpolated from the four low-resolution
-// neighbours in memory on each pass (bilerp(): the bits pp_bilinear_fwd writes)
+// LowresTile<false> (PPT = 4, no LDS patch): every class of a pixel is interpolated from the four low-resolution neighbours in
+// memory on each pass (LowresTaps::at(): the bits pp_bilinear_fwd writes)
 template <int MATH>
 __global__ __launch_bounds__(kBlock) void acq_lowres_stream_kernel(LowresParams p)
 {
@@ -1266,7 +1204,6 @@ __global__ __launch_bounds__(kBlock) void acq_lowres_stream_kernel(LowresParams 
     __shared__ uint64_t s_surv[kBlock / kWave][kSurvCap];
     __shared__ uint32_t s_cnt[kBlock / kWave];
     __shared__ uint64_t s_top[(kBlock / kWave) * kSmallKMax];
-    constexpr int TR = (kBlock / kWave) * PPT, TC = kWave;
     const int tiles = p.tiles_x * p.tiles_y;
     const int img = blockIdx.x / tiles;
     const int t = blockIdx.x - img * tiles;
@@ -1276,31 +1213,20 @@ __global__ __launch_bounds__(kBlock) void acq_lowres_stream_kernel(LowresParams 
     const bool largest = p.strategy != PP_ACQ_MARGIN;
     const float fill = largest ? 0.0f : 1.0f;
     const int64_t N = (int64_t)p.Hc * p.Wc;
-    const int X = tx * TC + lane;
-    const bool xin = X < p.Wc;
-    const Lerp lw = lerp_src(xin ? X : p.Wc - 1, p.w, p.sw, p.align);
+    LowresTile<false> tile(p, p.C, tx, ty, (kBlock / kWave) * PPT, kBlock);
+    tile.set_lane(p, lane);
     const float* base = p.low + (int64_t)img * p.h * p.w * p.ldx;
     const uint8_t* excl = p.exclude ? p.exclude + (int64_t)img * N : nullptr;
     float* omap = p.out_map ? p.out_map + (int64_t)img * N : nullptr;
     uint32_t kh[PPT], kl[PPT];
 #pragma unroll
     for (int j = 0; j < PPT; ++j) {
-        const int Y = ty * TR + wv * PPT + j;
-        if (Y < p.Hc && xin) {
-            const Lerp lh = lerp_src(Y, p.h, p.sh, p.align);
-            const float* p00 = base + ((int64_t)lh.i0 * p.w + lw.i0) * p.ldx;
-            const float* p01 = base + ((int64_t)lh.i0 * p.w + lw.i1) * p.ldx;
-            const float* p10 = base + ((int64_t)lh.i1 * p.w + lw.i0) * p.ldx;
-            const float* p11 = base + ((int64_t)lh.i1 * p.w + lw.i1) * p.ldx;
+        const int Y = tile.Y0 + wv * PPT + j;
+        if (Y < p.Hc && tile.xin) {
+            const auto tp = tile.taps(base, tile.row(p, Y));
             float s[1];
-            score_stream<1, MATH>([&](int c, float (&v)[1]) {
-                v[0] = bilerp(lh.l0, lh.l1, lw.l0, lw.l1, p00[c], p01[c], p10[c], p11[c]);
-            }, p.C, p.strategy, s);
-            const int64_t pix = (int64_t)Y * p.Wc + X;
-            if (excl && excl[pix]) s[0] = fill;
-            if (omap) omap[pix] = s[0];
-            kh[j] = order_key(s[0], largest);
-            kl[j] = 0xFFFFFFFFu - (uint32_t)pix;
+            score_stream<1, MATH>([&](int c, float (&v)[1]) { v[0] = tp.at(c); }, p.C, p.strategy, s);
+            lowres_emit_key(s[0], (int64_t)Y * p.Wc + tile.X, largest, fill, excl, omap, nullptr, 0.0f, kh[j], kl[j]);
         } else {
             kh[j] = 0u; kl[j] = 0u;
         }
@@ -1318,13 +1244,9 @@ __global__ __launch_bounds__(kBlock) void acq_lowres_at_stream_kernel(const floa
     const int pix = pix_idx[i], Y = pix / Wc, X = pix - Y * Wc;
     const Lerp lh = lerp_src(Y, h, sh, align), lw = lerp_src(X, w, sw, align);
     const float* base = low + (int64_t)img_idx[i] * h * w * ldx;
-    const float* p00 = base + ((int64_t)lh.i0 * w + lw.i0) * ldx;
-    const float* p01 = base + ((int64_t)lh.i0 * w + lw.i1) * ldx;
-    const float* p10 = base + ((int64_t)lh.i1 * w + lw.i0) * ldx;
-    const float* p11 = base + ((int64_t)lh.i1 * w + lw.i1) * ldx;
+    const auto tp = lowres_taps(base, ldx, w, lh, lw);
     float s[1];
-    score_stream<1, 0>([&](int c, float (&v)[1]) { v[0] = bilerp(lh.l0, lh.l1, lw.l0, lw.l1, p00[c], p01[c], p10[c], p11[c]); },
-                       C, strategy, s);
+    score_stream<1, 0>([&](int c, float (&v)[1]) { v[0] = tp.at(c); }, C, strategy, s);
     out[i] = s[0];
 }
 
@@ -2722,18 +2644,13 @@ static LowresPlan make_lowres_plan(int64_t B, int64_t C, int64_t h, int64_t w, i
     // x2 models (FPNSeg, decoders.py:101): a 32-row tile interpolates from 19 x 35 source pixels = 50.5 KB at C = 19; the 16-row
     // tile's patch (29 KB) keeps the LDS path and two more blocks per CU
     if (pl.ppt == 8 && g_tune_ppt != 8) {      // pp_debug_set_acq_tuning(., 4 | 8) forces a tile height (A/B)
-        const int64_t pw8 = std::min<int64_t>(w, (int64_t)std::ceil((double)sw * (kWave - 1)) + 3);
-        const int64_t ph8 = std::min<int64_t>(h, (int64_t)std::ceil((double)sh * ((kBlock / kWave) * 8 - 1)) + 3);
-        if ((size_t)(ph8 * pw8 * (C | 1)) * 4 > kLowresLdsSoft) pl.ppt = 4;
+        if ((size_t)lowres_patch_floats(sh, sw, h, w, (kBlock / kWave) * 8, C) * 4 > kLowresLdsSoft) pl.ppt = 4;
     }
     if (g_tune_ppt == 4) pl.ppt = 4;
     pl.tiles_x = (int)cdiv(Wc, kWave);
     pl.tiles_y = (int)cdiv(Hc, (kBlock / kWave) * pl.ppt);
     pl.waves_per_image = pl.tiles_x * pl.tiles_y;      // candidate lists per image: one per block (tile)
-    // a tile of T output pixels spans at most ceil(scale*(T-1)) + 3 source pixels (i0 of the first .. i1 of the last)
-    const int64_t pw = std::min<int64_t>(w, (int64_t)std::ceil((double)sw * (kWave - 1)) + 3);
-    const int64_t ph = std::min<int64_t>(h, (int64_t)std::ceil((double)sh * ((kBlock / kWave) * pl.ppt - 1)) + 3);
-    const int64_t fl = ph * pw * (C | 1);
+    const int64_t fl = lowres_patch_floats(sh, sw, h, w, (kBlock / kWave) * pl.ppt, C);
     pl.lds = (size_t)fl * 4 <= kLowresLdsMax;
     pl.patch_cap = pl.lds ? (int)fl : 0;
     pl.lds_bytes = pl.lds ? (size_t)fl * 4 : 0;
@@ -2781,14 +2698,7 @@ static int dispatch_lowres(const LowresParams& p, const LowresPlan& pl, int64_t 
         else                 hipLaunchKernelGGL((acq_lowres_stream_kernel<0>), grid, block, 0, st, p);
         return check_launch("acq_lowres_stream_kernel");
     }
-    switch (p.C) {
-        case 11: return launch_lowres<11, true>(p, pl, B, st);
-        case 19: return launch_lowres<19, true>(p, pl, B, st);
-        case 21: return launch_lowres<21, true>(p, pl, B, st);
-        default: break;
-    }
-    if (p.C <= 32) return launch_lowres<32, false>(p, pl, B, st);
-    return launch_lowres<64, false>(p, pl, B, st);
+    return lowres_by_classes(p.C, [&](auto cmax, auto exact) { return launch_lowres<decltype(cmax)::value, decltype(exact)::value>(p, pl, B, st); });
 }
 
 static int validate_lowres(const float* low, int64_t ldx, int64_t B, int64_t C, int64_t h, int64_t w, int64_t H, int64_t W,
@@ -2854,14 +2764,7 @@ static int launch_lowres_mc(const LowresMcParams& q, const LowresPlan& pl, int64
 
 static int dispatch_lowres_mc(const LowresMcParams& q, const LowresPlan& pl, int64_t B, hipStream_t st)
 {
-    switch (q.g.C) {
-        case 11: return launch_lowres_mc<11, true>(q, pl, B, st);
-        case 19: return launch_lowres_mc<19, true>(q, pl, B, st);
-        case 21: return launch_lowres_mc<21, true>(q, pl, B, st);
-        default: break;
-    }
-    if (q.g.C <= 32) return launch_lowres_mc<32, false>(q, pl, B, st);
-    return launch_lowres_mc<64, false>(q, pl, B, st);
+    return lowres_by_classes(q.g.C, [&](auto cmax, auto exact) { return launch_lowres_mc<decltype(cmax)::value, decltype(exact)::value>(q, pl, B, st); });
 }
 
 // ---- MC-dropout hard vote: host side ---------------------------------------------------------------------
@@ -2908,14 +2811,50 @@ static int launch_lowres_mc_vote(const LowresVoteParams& q, const LowresPlan& pl
 
 static int dispatch_lowres_mc_vote(const LowresVoteParams& q, const LowresPlan& pl, int64_t B, hipStream_t st)
 {
-    switch (q.g.C) {
-        case 11: return launch_lowres_mc_vote<11, true>(q, pl, B, st);
-        case 19: return launch_lowres_mc_vote<19, true>(q, pl, B, st);
-        case 21: return launch_lowres_mc_vote<21, true>(q, pl, B, st);
-        default: break;
+    return lowres_by_classes(q.g.C, [&](auto cmax, auto exact) { return launch_lowres_mc_vote<decltype(cmax)::value, decltype(exact)::value>(q, pl, B, st); });
+}
+
+// The body the three low-resolution *_topk entries share, after their own validation.  `launch` runs the entry's scorer with the
+// finished p (plan, map, candidate lists or histogram filled in): map only (k == 0); k <= 48: per-tile candidate lists + merge;
+// larger k: the score map (the caller's, or the workspace's) + the large-k selection on it at `qscale`, with the quantised
+// histogram counted by the scorer itself where the entry allows it (hist_ok).
+template <typename Launch>
+static int run_lowres_select(LowresParams& p, const LowresPlan& pl, int64_t B, int64_t k, int32_t* out_idx, float* out_val, void* workspace,
+                             size_t ws_bytes, hipStream_t st, float qscale, bool hist_ok, Launch launch)
+{
+    const int64_t N = (int64_t)p.Hc * p.Wc;
+    p.tiles_x = pl.tiles_x; p.tiles_y = pl.tiles_y; p.patch_cap = pl.patch_cap;
+    if (k == 0) {     // score map only
+        if (!p.out_map) return fail(PP_ERR_BAD_ARG, "k == 0 (map only) needs out_map");
+        return launch();
     }
-    if (q.g.C <= 32) return launch_lowres_mc_vote<32, false>(q, pl, B, st);
-    return launch_lowres_mc_vote<64, false>(q, pl, B, st);
+    if (k < 1 || k > N) return fail(PP_ERR_BAD_K, "k=%lld outside [1, H*W=%lld]", (long long)k, (long long)N);
+    if (!out_idx) return fail(PP_ERR_BAD_ARG, "out_idx is null");
+    const size_t need = pp_acq_lowres_workspace_bytes(B, p.C, p.Hc, p.Wc, k);
+    if (!workspace || ws_bytes < need)
+        return fail(PP_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, need);
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(PP_ERR_BAD_ARG, "workspace must be 256-B aligned");
+    const int largest = p.strategy != PP_ACQ_MARGIN;
+    if (k <= kSmallKMax) {
+        const int64_t n_cand = (int64_t)pl.waves_per_image * k;
+        uint64_t* cand = reinterpret_cast<uint64_t*>(workspace);
+        uint64_t* other = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(workspace) +
+                                                      align_up((size_t)B * n_cand * 8, 256));
+        p.cand = cand;
+        p.k = (int)k;
+        if (int rc = launch()) return rc;
+        return run_merge(cand, n_cand, other, B, (int)k, largest, out_idx, out_val, st);
+    }
+    float* map = p.out_map ? p.out_map : reinterpret_cast<float*>(workspace);
+    uint64_t* gbuf = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(workspace) + align_up((size_t)B * N * 4, 256));
+    p.out_map = map;
+    if (hist_ok) {
+        p.qhist = large_hist(gbuf, B, k);
+        p.qscale = qscale;
+        if (hipMemsetAsync(p.qhist, 0, (size_t)B * kQBins * 4, st) != hipSuccess) return fail(PP_ERR_LAUNCH, "topk: memset failed");
+    }
+    if (int rc = launch()) return rc;
+    return run_large(map, B, N, k, largest, gbuf, out_idx, out_val, st, qscale, hist_ok);
 }
 
 }  // namespace pp
@@ -3089,49 +3028,15 @@ int pp_acq_lowres_score_topk(const float* low, int64_t ldx, int64_t B, int64_t C
 {
     const ExactScope exact_scope(strategy);
     if (int rc = validate_lowres(low, ldx, B, C, h, w, H, W, Hc, Wc, strategy)) return rc;
-    const int64_t N = Hc * Wc;
     hipStream_t st = as_stream(stream);
     float sh, sw;
     lowres_scales(h, w, H, W, align_corners, sh, sw);
     LowresParams p{low, ldx, exclude, out_map, nullptr, (int)h, (int)w, (int)Hc, (int)Wc, sh, sw, align_corners ? 1 : 0,
                    (int)C, 0, 0, 0, strategy, g_reduce_mode, 0};
-    if (k == 0) {     // score map only
-        if (!out_map) return fail(PP_ERR_BAD_ARG, "k == 0 (map only) needs out_map");
-        LowresPlan pl = make_lowres_plan(B, C, h, w, Hc, Wc, sh, sw, exact_formula() != 0 || stream_classes(C));
-        p.tiles_x = pl.tiles_x; p.tiles_y = pl.tiles_y; p.patch_cap = pl.patch_cap;
-        return dispatch_lowres(p, pl, B, st);
-    }
-    if (k < 1 || k > N) return fail(PP_ERR_BAD_K, "k=%lld outside [1, H*W=%lld]", (long long)k, (long long)N);
-    if (!out_idx) return fail(PP_ERR_BAD_ARG, "out_idx is null");
-    const size_t need = pp_acq_lowres_workspace_bytes(B, C, Hc, Wc, k);
-    if (!workspace || ws_bytes < need)
-        return fail(PP_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, need);
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(PP_ERR_BAD_ARG, "workspace must be 256-B aligned");
-    const int largest = strategy != PP_ACQ_MARGIN;
-    LowresPlan pl = make_lowres_plan(B, C, h, w, Hc, Wc, sh, sw, exact_formula() != 0 || stream_classes(C));
-    p.tiles_x = pl.tiles_x; p.tiles_y = pl.tiles_y; p.patch_cap = pl.patch_cap;
-    if (k <= kSmallKMax) {
-        const int64_t n_cand = (int64_t)pl.waves_per_image * k;
-        uint64_t* cand = reinterpret_cast<uint64_t*>(workspace);
-        uint64_t* other = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(workspace) +
-                                                      align_up((size_t)B * n_cand * 8, 256));
-        p.cand = cand;
-        p.k = (int)k;
-        if (int rc = dispatch_lowres(p, pl, B, st)) return rc;
-        return run_merge(cand, n_cand, other, B, (int)k, largest, out_idx, out_val, st);
-    }
-    float* map = out_map ? out_map : reinterpret_cast<float*>(workspace);
-    uint64_t* gbuf = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(workspace) + align_up((size_t)B * N * 4, 256));
-    p.out_map = map;
+    const LowresPlan pl = make_lowres_plan(B, C, h, w, Hc, Wc, sh, sw, exact_formula() != 0 || stream_classes(C));
     const float qs = score_qscale(strategy, C);
-    const bool fuse_hist = g_hist_fuse && large_q_ok(B, k, qs) && !stream_classes(C);      // (acq_lowres_kernel only: the streamed form has no histogram epilogue)
-    if (fuse_hist) {
-        p.qhist = large_hist(gbuf, B, k);
-        p.qscale = qs;
-        if (hipMemsetAsync(p.qhist, 0, (size_t)B * kQBins * 4, st) != hipSuccess) return fail(PP_ERR_LAUNCH, "topk: memset failed");
-    }
-    if (int rc = dispatch_lowres(p, pl, B, st)) return rc;
-    return run_large(map, B, N, k, largest, gbuf, out_idx, out_val, st, qs, fuse_hist);
+    const bool hist_ok = g_hist_fuse && large_q_ok(B, k, qs) && !stream_classes(C);      // (acq_lowres_kernel only: the streamed form has no histogram epilogue)
+    return run_lowres_select(p, pl, B, k, out_idx, out_val, workspace, ws_bytes, st, qs, hist_ok, [&] { return dispatch_lowres(p, pl, B, st); });
 }
 
 int pp_acq_lowres_score_at(const float* low, int64_t ldx, int64_t B, int64_t C, int64_t h, int64_t w, int64_t H,
@@ -3147,23 +3052,16 @@ int pp_acq_lowres_score_at(const float* low, int64_t ldx, int64_t B, int64_t C, 
     hipStream_t st = as_stream(stream);
     dim3 grid((unsigned)cdiv(n, kBlock)), block(kBlock);
     const int al = align_corners ? 1 : 0;
-#define PP_AT(CM, EX)                                                                                                   \
-    hipLaunchKernelGGL((acq_lowres_at_kernel<CM, EX>), grid, block, 0, st, low, ldx, (int)h, (int)w, sh, sw, al, (int)Wc, \
-                       (int)C, strategy, img_idx, pix_idx, n, out)
     if (stream_classes(C)) {
         hipLaunchKernelGGL(acq_lowres_at_stream_kernel, grid, block, 0, st, low, ldx, (int)h, (int)w, sh, sw, al, (int)Wc, (int)C, strategy,
                            img_idx, pix_idx, n, out);
         return check_launch("acq_lowres_at_stream_kernel");
     }
-    switch (C) {
-        case 11: PP_AT(11, true); break;
-        case 19: PP_AT(19, true); break;
-        case 21: PP_AT(21, true); break;
-        default:
-            if (C <= 32) PP_AT(32, false);
-            else PP_AT(64, false);
-    }
-#undef PP_AT
+    lowres_by_classes(C, [&](auto cmax, auto exact) {
+        hipLaunchKernelGGL((acq_lowres_at_kernel<decltype(cmax)::value, decltype(exact)::value>), grid, block, 0, st, low, ldx, (int)h, (int)w, sh,
+                           sw, al, (int)Wc, (int)C, strategy, img_idx, pix_idx, n, out);
+        return 0;
+    });
     return check_launch("acq_lowres_at_kernel");
 }
 
@@ -3173,49 +3071,16 @@ int pp_acq_lowres_mc_score_topk(const float* low, int64_t ldx, int64_t B, int64_
                                 size_t ws_bytes, pp_stream_t stream)
 {
     if (int rc = validate_lowres_mc(low, ldx, B, T, C, h, w, H, W, Hc, Wc, strategy)) return rc;
-    const int64_t N = Hc * Wc;
     hipStream_t st = as_stream(stream);
     float sh, sw;
     lowres_scales(h, w, H, W, align_corners, sh, sw);
     LowresMcParams q{{low, ldx, exclude, out_map, nullptr, (int)h, (int)w, (int)Hc, (int)Wc, sh, sw, align_corners ? 1 : 0,
                       (int)C, 0, 0, 0, strategy, g_reduce_mode, 0}, (int)T, scale};
-    LowresParams& p = q.g;
     const LowresPlan pl = make_lowres_mc_plan(B, C, h, w, Hc, Wc, sh, sw);
-    p.tiles_x = pl.tiles_x; p.tiles_y = pl.tiles_y; p.patch_cap = pl.patch_cap;
-    if (k == 0) {     // score map only
-        if (!out_map) return fail(PP_ERR_BAD_ARG, "k == 0 (map only) needs out_map");
-        return dispatch_lowres_mc(q, pl, B, st);
-    }
-    if (k < 1 || k > N) return fail(PP_ERR_BAD_K, "k=%lld outside [1, H*W=%lld]", (long long)k, (long long)N);
-    if (!out_idx) return fail(PP_ERR_BAD_ARG, "out_idx is null");
-    const size_t need = pp_acq_lowres_workspace_bytes(B, C, Hc, Wc, k);
-    if (!workspace || ws_bytes < need)
-        return fail(PP_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, need);
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(PP_ERR_BAD_ARG, "workspace must be 256-B aligned");
-    const int largest = strategy != PP_ACQ_MARGIN;
-    if (k <= kSmallKMax) {
-        const int64_t n_cand = (int64_t)pl.waves_per_image * k;
-        uint64_t* cand = reinterpret_cast<uint64_t*>(workspace);
-        uint64_t* other = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(workspace) +
-                                                      align_up((size_t)B * n_cand * 8, 256));
-        p.cand = cand;
-        p.k = (int)k;
-        if (int rc = dispatch_lowres_mc(q, pl, B, st)) return rc;
-        return run_merge(cand, n_cand, other, B, (int)k, largest, out_idx, out_val, st);
-    }
     // the mean of T scores lies in the score's own range: the quantised-histogram select applies unchanged
-    float* map = out_map ? out_map : reinterpret_cast<float*>(workspace);
-    uint64_t* gbuf = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(workspace) + align_up((size_t)B * N * 4, 256));
-    p.out_map = map;
     const float qs = score_qscale(strategy, C);
-    const bool fuse_hist = g_hist_fuse && large_q_ok(B, k, qs);
-    if (fuse_hist) {
-        p.qhist = large_hist(gbuf, B, k);
-        p.qscale = qs;
-        if (hipMemsetAsync(p.qhist, 0, (size_t)B * kQBins * 4, st) != hipSuccess) return fail(PP_ERR_LAUNCH, "topk: memset failed");
-    }
-    if (int rc = dispatch_lowres_mc(q, pl, B, st)) return rc;
-    return run_large(map, B, N, k, largest, gbuf, out_idx, out_val, st, qs, fuse_hist);
+    const bool hist_ok = g_hist_fuse && large_q_ok(B, k, qs);
+    return run_lowres_select(q.g, pl, B, k, out_idx, out_val, workspace, ws_bytes, st, qs, hist_ok, [&] { return dispatch_lowres_mc(q, pl, B, st); });
 }
 
 int pp_acq_lowres_mc_score_at(const float* low, int64_t ldx, int64_t B, int64_t T, int64_t C, int64_t h, int64_t w, int64_t H,
@@ -3230,18 +3095,11 @@ int pp_acq_lowres_mc_score_at(const float* low, int64_t ldx, int64_t B, int64_t 
     hipStream_t st = as_stream(stream);
     dim3 grid((unsigned)cdiv(n, kBlock)), block(kBlock);
     const int al = align_corners ? 1 : 0;
-#define PP_MC_AT(CM, EX)                                                                                                             \
-    hipLaunchKernelGGL((acq_lowres_mc_at_kernel<CM, EX>), grid, block, 0, st, low, ldx, (int)T, (int)h, (int)w, sh, sw, al, (int)Wc, \
-                       (int)C, strategy, scale, img_idx, pix_idx, n, out)
-    switch (C) {
-        case 11: PP_MC_AT(11, true); break;
-        case 19: PP_MC_AT(19, true); break;
-        case 21: PP_MC_AT(21, true); break;
-        default:
-            if (C <= 32) PP_MC_AT(32, false);
-            else PP_MC_AT(64, false);
-    }
-#undef PP_MC_AT
+    lowres_by_classes(C, [&](auto cmax, auto exact) {
+        hipLaunchKernelGGL((acq_lowres_mc_at_kernel<decltype(cmax)::value, decltype(exact)::value>), grid, block, 0, st, low, ldx, (int)T, (int)h,
+                           (int)w, sh, sw, al, (int)Wc, (int)C, strategy, scale, img_idx, pix_idx, n, out);
+        return 0;
+    });
     return check_launch("acq_lowres_mc_at_kernel");
 }
 
@@ -3279,44 +3137,16 @@ int pp_acq_lowres_mc_vote_topk(const float* low, int64_t ldx, int64_t B, int64_t
     if (!low) return fail(PP_ERR_BAD_ARG, "logits is null");
     if (int rc = validate_vote_passes(T)) return rc;
     if (int rc = validate_lowres_mc(low, ldx, B, T, C, h, w, H, W, Hc, Wc, strategy)) return rc;
-    const int64_t N = Hc * Wc;
     hipStream_t st = as_stream(stream);
     float sh, sw;
     lowres_scales(h, w, H, W, align_corners, sh, sw);
     LowresVoteParams q{{low, ldx, exclude, out_map, nullptr, (int)h, (int)w, (int)Hc, (int)Wc, sh, sw, align_corners ? 1 : 0,
                         (int)C, 0, 0, 0, strategy, g_reduce_mode, 0}, (int)T, {}};
     fill_vote_table(T, q.tab);
-    LowresParams& p = q.g;
     const LowresPlan pl = make_lowres_mc_plan(B, C, h, w, Hc, Wc, sh, sw);
-    p.tiles_x = pl.tiles_x; p.tiles_y = pl.tiles_y; p.patch_cap = pl.patch_cap;
-    if (k == 0) {     // score map only
-        if (!out_map) return fail(PP_ERR_BAD_ARG, "k == 0 (map only) needs out_map");
-        return dispatch_lowres_mc_vote(q, pl, B, st);
-    }
-    if (k < 1 || k > N) return fail(PP_ERR_BAD_K, "k=%lld outside [1, H*W=%lld]", (long long)k, (long long)N);
-    if (!out_idx) return fail(PP_ERR_BAD_ARG, "out_idx is null");
-    const size_t need = pp_acq_lowres_workspace_bytes(B, C, Hc, Wc, k);
-    if (!workspace || ws_bytes < need)
-        return fail(PP_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, need);
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(PP_ERR_BAD_ARG, "workspace must be 256-B aligned");
-    const int largest = strategy != PP_ACQ_MARGIN;
-    if (k <= kSmallKMax) {
-        const int64_t n_cand = (int64_t)pl.waves_per_image * k;
-        uint64_t* cand = reinterpret_cast<uint64_t*>(workspace);
-        uint64_t* other = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(workspace) +
-                                                      align_up((size_t)B * n_cand * 8, 256));
-        p.cand = cand;
-        p.k = (int)k;
-        if (int rc = dispatch_lowres_mc_vote(q, pl, B, st)) return rc;
-        return run_merge(cand, n_cand, other, B, (int)k, largest, out_idx, out_val, st);
-    }
-    // k > 48: the map, then pp_topk_select's selection on it - without the scorers' fused histogram, whose bins clamp the fills
-    // (-1.0 / 2.0 lie outside the score range) into the end bins
-    float* map = out_map ? out_map : reinterpret_cast<float*>(workspace);
-    uint64_t* gbuf = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(workspace) + align_up((size_t)B * N * 4, 256));
-    p.out_map = map;
-    if (int rc = dispatch_lowres_mc_vote(q, pl, B, st)) return rc;
-    return run_large(map, B, N, k, largest, gbuf, out_idx, out_val, st);
+    // k > 48: the map, then pp_topk_select's selection on it (qscale 0) - without the scorers' fused histogram, whose bins clamp the
+    // fills (-1.0 / 2.0 lie outside the score range) into the end bins
+    return run_lowres_select(q.g, pl, B, k, out_idx, out_val, workspace, ws_bytes, st, 0.0f, false, [&] { return dispatch_lowres_mc_vote(q, pl, B, st); });
 }
 
 int pp_topk_select(const float* scores, int64_t B, int64_t N, int64_t k, int largest, int32_t* out_idx,

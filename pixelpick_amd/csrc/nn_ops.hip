@@ -15,6 +15,7 @@
 //   Adam step                    utils/utils.py:125-141 (torch.optim.Adam semantics) (L4)
 #include "pp_common.h"
 #include "bn_xchg.h"
+#include "lowres_tile.h"
 
 namespace pp {
 
@@ -1976,19 +1977,6 @@ __global__ __launch_bounds__(kT) void ce_bwd_kernel(const float* logits, const i
 // footprint (fixed order, no atomics: bitwise reproducible).
 // ================================================================================================
 template <int CMAX, bool EXACT>
-__device__ __forceinline__ void lowres_class_vector(const float* base, int64_t ldx, int w, const Lerp& lh, const Lerp& lw, int C,
-                                                    float (&x)[CMAX])
-{
-    const float* p00 = base + ((int64_t)lh.i0 * w + lw.i0) * ldx;
-    const float* p01 = base + ((int64_t)lh.i0 * w + lw.i1) * ldx;
-    const float* p10 = base + ((int64_t)lh.i1 * w + lw.i0) * ldx;
-    const float* p11 = base + ((int64_t)lh.i1 * w + lw.i1) * ldx;
-#pragma unroll
-    for (int c = 0; c < CMAX; ++c)
-        if (EXACT || c < C) x[c] = bilerp(lh.l0, lh.l1, lw.l0, lw.l1, p00[c], p01[c], p10[c], p11[c]);
-}
-
-template <int CMAX, bool EXACT>
 __global__ __launch_bounds__(kT) void ce_lowres_partial_kernel(const float* low, int64_t ldx, int B, int C, int h, int w, int H,
                                                               int W, float sh, float sw, int align, const int64_t* target,
                                                               int ignore_index, float* part /*[nblk][2]*/)
@@ -2002,7 +1990,7 @@ __global__ __launch_bounds__(kT) void ce_lowres_partial_kernel(const float* low,
         const int64_t b = e / HW, pix = e - b * HW;
         const int Y = (int)(pix / W), X = (int)(pix - (int64_t)Y * W);
         float x[CMAX];
-        lowres_class_vector<CMAX, EXACT>(low + b * h * w * ldx, ldx, w, lerp_src(Y, h, sh, align), lerp_src(X, w, sw, align), C, x);
+        lowres_class_vector<CMAX, EXACT>(lowres_taps(low + b * h * w * ldx, ldx, w, lerp_src(Y, h, sh, align), lerp_src(X, w, sw, align)), C, x);
         float m = x[0], xt = 0.0f;
 #pragma unroll
         for (int c = 1; c < CMAX; ++c)
@@ -2081,7 +2069,7 @@ __global__ __launch_bounds__(kT) void ce_lowres_bwd_kernel(const float* low, int
             if (lw.i0 != c0 && lw.i1 != c0) continue;
             const float ww = (lw.i0 == c0 ? lw.l0 : 0.0f) + (lw.i1 == c0 ? lw.l1 : 0.0f);
             float x[CMAX];
-            lowres_class_vector<CMAX, EXACT>(base, ldx, w, lh, lw, C, x);
+            lowres_class_vector<CMAX, EXACT>(lowres_taps(base, ldx, w, lh, lw), C, x);
             float m = x[0];
 #pragma unroll
             for (int c = 1; c < CMAX; ++c)
@@ -2111,25 +2099,8 @@ __global__ __launch_bounds__(kT) void ce_lowres_bwd_kernel(const float* low, int
 // the data set configuration) walk the four taps' class vectors - contiguous in the channels-last tensor - from memory instead:
 // pass 1 the maximum, pass 2 the sum of exponentials (the same 4*C floats again, served by the cache), in the register kernels'
 // operation order (ascending classes, one running sum), so that on a narrow head the two forms agree to the last bit.
-struct CeTaps {
-    const float *p00, *p01, *p10, *p11;
-    float h0, h1, w0, w1;
-    __device__ __forceinline__ float at(int c) const { return bilerp(h0, h1, w0, w1, p00[c], p01[c], p10[c], p11[c]); }
-};
-
-__device__ __forceinline__ CeTaps ce_taps(const float* base, int64_t ldx, int w, const Lerp& lh, const Lerp& lw)
-{
-    CeTaps t;
-    t.p00 = base + ((int64_t)lh.i0 * w + lw.i0) * ldx;
-    t.p01 = base + ((int64_t)lh.i0 * w + lw.i1) * ldx;
-    t.p10 = base + ((int64_t)lh.i1 * w + lw.i0) * ldx;
-    t.p11 = base + ((int64_t)lh.i1 * w + lw.i1) * ldx;
-    t.h0 = lh.l0; t.h1 = lh.l1; t.w0 = lw.l0; t.w1 = lw.l1;
-    return t;
-}
-
 // m = max_c x_c, S = sum_c exp(x_c - m), xt = x_tg (0 when tg is no class) of one interpolated pixel
-__device__ __forceinline__ void ce_stream_stats(const CeTaps& t, int C, int64_t tg, float& m, float& S, float& xt)
+__device__ __forceinline__ void ce_stream_stats(const LowresTaps<>& t, int C, int64_t tg, float& m, float& S, float& xt)
 {
     m = t.at(0);
 #pragma unroll 8
@@ -2156,7 +2127,7 @@ __global__ __launch_bounds__(kT) void ce_lowres_stream_partial_kernel(const floa
         if (tg == ignore_index) continue;
         const int64_t b = e / HW, pix = e - b * HW;
         const int Y = (int)(pix / W), X = (int)(pix - (int64_t)Y * W);
-        const CeTaps t = ce_taps(low + b * h * w * ldx, ldx, w, lerp_src(Y, h, sh, align), lerp_src(X, w, sw, align));
+        const auto t = lowres_taps(low + b * h * w * ldx, ldx, w, lerp_src(Y, h, sh, align), lerp_src(X, w, sw, align));
         float m, S, xt;
         ce_stream_stats(t, C, tg, m, S, xt);
         ls += (m + logf(S)) - xt;
@@ -2214,7 +2185,7 @@ __global__ __launch_bounds__(kT) void ce_lowres_stream_bwd_kernel(const float* l
             const Lerp lw = lerp_src(X, w, sw, align);
             if (lw.i0 != c0 && lw.i1 != c0) continue;
             const float ww = (lw.i0 == c0 ? lw.l0 : 0.0f) + (lw.i1 == c0 ? lw.l1 : 0.0f);
-            const CeTaps tp = ce_taps(base, ldx, w, lh, lw);
+            const auto tp = lowres_taps(base, ldx, w, lh, lw);
             float m, S, xt;
             ce_stream_stats(tp, C, tg, m, S, xt);
             const float inv = 1.0f / S, wgt = wh * ww;

@@ -6,12 +6,13 @@
 // without writing the [B,C,H,W] logits: at 256x512x19 that tensor is 10 MB written and read back per image to be reduced to one
 // byte per pixel; the inputs needed are 0.62 MB of 64x128x19 logits and the labels.
 //
-// Geometry is acq_lowres_kernel's (acq.hip): a block owns 64 output columns x (4 waves x ppt rows), stages the low-resolution
-// patch the tile interpolates from in LDS with an odd pixel pitch, and every lane interpolates its pixels with bilerp() - the
-// bits pp_bilinear_fwd writes.  Unlike the scorer, argmax needs only a running maximum: the classes are a run-time loop, no
+// Geometry is LowresTile's (lowres_tile.h): a block owns 64 output columns x (4 waves x ppt rows), stages the low-resolution
+// patch the tile interpolates from in LDS, and every lane interpolates its pixels from the tile's taps - the bits
+// pp_bilinear_fwd writes.  Unlike the scorer, argmax needs only a running maximum: the classes are a run-time loop, no
 // class vector lives in registers and there is no per-C instantiation.  Blocks walk the tiles with a grid stride so that the
 // block-private C x C histogram is flushed (64-bit integer atomics, non-zero cells only) by at most kPredMaxBlocks blocks.
 #include "pp_common.h"
+#include "lowres_tile.h"
 
 #include <algorithm>
 #include <cmath>
@@ -115,8 +116,7 @@ __global__ __launch_bounds__(kPredBlock) void predict_lowres_kernel(PredictParam
         for (int i = tid; i < C * C; i += kPredBlock) s_hist[i] = 0u;
         __syncthreads();
     }
-    const int CP = C | 1;                     // odd pixel pitch: lanes on neighbouring source columns hit different banks
-    const int TR = kPredWaves * p.ppt, TC = kWave;
+    const int TR = kPredWaves * p.ppt;
     const int tiles = p.tiles_x * p.tiles_y;
     const int64_t N = (int64_t)p.Hc * p.Wc;
 
@@ -124,51 +124,32 @@ __global__ __launch_bounds__(kPredBlock) void predict_lowres_kernel(PredictParam
         const int64_t img = blk / tiles;
         const int t = (int)(blk - img * tiles);
         const int ty = t / p.tiles_x, tx = t - ty * p.tiles_x;
-        const int X0 = tx * TC, Y0 = ty * TR;
-        const int X1 = min(X0 + TC - 1, p.Wc - 1), Y1 = min(Y0 + TR - 1, p.Hc - 1);
+        LowresTile<LDS> tile(p, C, tx, ty, TR, kPredBlock);
         const float* base = p.low + img * p.h * p.w * p.ldx;
-        int c_lo = 0, r_lo = 0, pw = p.w;
         if constexpr (LDS) {
-            c_lo = lerp_src(X0, p.w, p.sw, p.align).i0;
-            r_lo = lerp_src(Y0, p.h, p.sh, p.align).i0;
-            const int c_hi = lerp_src(X1, p.w, p.sw, p.align).i1, r_hi = lerp_src(Y1, p.h, p.sh, p.align).i1;
-            pw = c_hi - c_lo + 1;
-            const int ph = r_hi - r_lo + 1;
-            if (ph * pw * CP > p.patch_cap) __builtin_trap();   // host sizing bug: never silently write past the patch
             if (blk != blockIdx.x) __syncthreads();             // the previous tile's readers are done with the patch
-            const int n = ph * pw * C;
-            for (int e = tid; e < n; e += kPredBlock) {
-                const int pc = e / C, ch = e - pc * C;
-                const int r = pc / pw, c = pc - r * pw;
-                s_patch[pc * CP + ch] = base[((int64_t)(r_lo + r) * p.w + c_lo + c) * p.ldx + ch];
-            }
+            tile.stage(p, s_patch, base);
             __syncthreads();
         }
-        const int X = X0 + lane;
-        const bool xin = X < p.Wc;
-        const Lerp lw = lerp_src(xin ? X : X1, p.w, p.sw, p.align);
-        const int64_t pitch = LDS ? (int64_t)CP : p.ldx;
-        const int64_t o0 = (int64_t)(lw.i0 - c_lo) * pitch, o1 = (int64_t)(lw.i1 - c_lo) * pitch;
+        tile.set_lane(p, lane);
         const float* src = LDS ? s_patch : base;
-        const int64_t row_pitch = (int64_t)pw * pitch;
-        const int Yw = Y0 + wv * p.ppt;                          // the wave's rows: Yw .. Yw + nrows - 1 (wave-uniform)
+        const int Yw = tile.Y0 + wv * p.ppt;                         // the wave's rows: Yw .. Yw + nrows - 1 (wave-uniform)
         const int nrows = min(p.ppt, p.Hc - Yw);
 #pragma unroll 1
         for (int j = 0; j < nrows;) {
             const int Y = Yw + j;
-            const Lerp lh = lerp_src(Y, p.h, p.sh, p.align);
+            const Lerp lh = tile.row(p, Y);
             int g = 1;                                           // rows from Y on that share lh's source rows (i1 follows from i0)
-            while (g < 4 && j + g < nrows && lerp_src(Y + g, p.h, p.sh, p.align).i0 == lh.i0) ++g;
-            const float* r0 = src + (int64_t)(lh.i0 - r_lo) * row_pitch;
-            const float* r1 = src + (int64_t)(lh.i1 - r_lo) * row_pitch;
+            while (g < 4 && j + g < nrows && tile.row(p, Y + g).i0 == lh.i0) ++g;
+            const auto tp = tile.taps(src, lh);
             if (g == 4) {
-                predict_rows<4, HIST>(p, r0 + o0, r0 + o1, r1 + o0, r1 + o1, lw.l0, lw.l1, Y, X, xin, img * N, s_hist, lane);
+                predict_rows<4, HIST>(p, tp.r0 + tp.o0, tp.r0 + tp.o1, tp.r1 + tp.o0, tp.r1 + tp.o1, tp.w0, tp.w1, Y, tile.X, tile.xin, img * N, s_hist, lane);
                 j += 4;
             } else if (g >= 2) {
-                predict_rows<2, HIST>(p, r0 + o0, r0 + o1, r1 + o0, r1 + o1, lw.l0, lw.l1, Y, X, xin, img * N, s_hist, lane);
+                predict_rows<2, HIST>(p, tp.r0 + tp.o0, tp.r0 + tp.o1, tp.r1 + tp.o0, tp.r1 + tp.o1, tp.w0, tp.w1, Y, tile.X, tile.xin, img * N, s_hist, lane);
                 j += 2;
             } else {
-                predict_rows<1, HIST>(p, r0 + o0, r0 + o1, r1 + o0, r1 + o1, lw.l0, lw.l1, Y, X, xin, img * N, s_hist, lane);
+                predict_rows<1, HIST>(p, tp.r0 + tp.o0, tp.r0 + tp.o1, tp.r1 + tp.o0, tp.r1 + tp.o1, tp.w0, tp.w1, Y, tile.X, tile.xin, img * N, s_hist, lane);
                 j += 1;
             }
         }
@@ -219,13 +200,8 @@ int pp_predict_lowres(const float* low, int64_t ldx, int64_t B, int64_t C, int64
     lowres_scales(h, w, H, W, align_corners, p.sh, p.sw);
     p.align = align_corners ? 1 : 0; p.target_kind = target_kind; p.C = (int)C;
 
-    // a tile of T output pixels spans at most ceil(scale*(T-1)) + 3 source pixels (i0 of the first .. i1 of the last)
     const size_t hist_bytes = hist ? (size_t)(C * C) * 4 : 0;
-    auto patch_floats = [&](int ppt) {
-        const int64_t pw = std::min<int64_t>(w, (int64_t)std::ceil((double)p.sw * (kWave - 1)) + 3);
-        const int64_t ph = std::min<int64_t>(h, (int64_t)std::ceil((double)p.sh * (kPredWaves * ppt - 1)) + 3);
-        return ph * pw * (C | 1);
-    };
+    auto patch_floats = [&](int ppt) { return lowres_patch_floats(p.sh, p.sw, h, w, kPredWaves * ppt, C); };
     p.tiles_x = (int)cdiv(Wc, kWave);
     const int64_t tiles8 = p.tiles_x * cdiv(Hc, kPredWaves * 8);
     p.ppt = (B * tiles8 >= 256 && hist_bytes + (size_t)patch_floats(8) * 4 <= kPredLdsSoft) ? 8 : 4;

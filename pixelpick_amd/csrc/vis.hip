@@ -7,9 +7,9 @@
 // and panel.  Resize and PNG encoding stay on the host (utils/utils.py:418-432).
 //
 // Two launches on the stream:
-//   vis_score_kernel   acq_lowres_kernel's / predict_lowres_kernel's tile: a block owns 64 output columns x (4 waves x ppt rows),
-//                      stages the low-resolution patch in LDS at odd pixel pitch, every lane interpolates its pixels' class vectors
-//                      with bilerp().  argmax (first maximum: pp_predict_lowres's bits) -> prediction panel; label -> target panel;
+//   vis_score_kernel   LowresTile (lowres_tile.h): a block owns 64 output columns x (4 waves x ppt rows), stages the
+//                      low-resolution patch in LDS, every lane interpolates its pixels' class vectors from the tile's taps.
+//                      argmax (first maximum: pp_predict_lowres's bits) -> prediction panel; label -> target panel;
 //                      pixel_score_fast (acq_score.h: pp_acq_lowres_score_topk's bits) x 3 -> fp32 scores in the workspace; the
 //                      block's min / max of the three scores and of its input pixels -> its own row of a slab in the workspace
 //                      (no atomics, nothing to initialise, reproducible).
@@ -18,6 +18,7 @@
 //                      every operation rounded on its own in fp32, as torch does on the CPU.
 #include "pp_common.h"
 #include "acq_score.h"
+#include "lowres_tile.h"
 
 #include <algorithm>
 #include <cmath>
@@ -74,33 +75,15 @@ __global__ __launch_bounds__(kVisBlock, 2) void vis_score_kernel(VisParams p)
     const int tid = threadIdx.x, lane = tid & (kWave - 1);
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int C = EXACT ? CMAX : p.C;
-    const int CP = C | 1;                     // odd pixel pitch: lanes on neighbouring source columns hit different banks
-    const int TR = kVisWaves * p.ppt, TC = kWave;
     const int64_t N = (int64_t)p.Hc * p.Wc;
-    const int X0 = tx * TC, Y0 = ty * TR;
-    const int X1 = min(X0 + TC - 1, p.Wc - 1), Y1 = min(Y0 + TR - 1, p.Hc - 1);
-    const int c_lo = lerp_src(X0, p.w, p.sw, p.align).i0, c_hi = lerp_src(X1, p.w, p.sw, p.align).i1;
-    const int r_lo = lerp_src(Y0, p.h, p.sh, p.align).i0, r_hi = lerp_src(Y1, p.h, p.sh, p.align).i1;
-    const int pw = c_hi - c_lo + 1, ph = r_hi - r_lo + 1;
+    LowresTile<LDS> tile(p, C, tx, ty, kVisWaves * p.ppt, kVisBlock);
     const float* base = p.low + (int64_t)img * p.h * p.w * p.ldx;
     for (int i = tid; i < 768; i += kVisBlock) s_pal[i] = p.palette[i];
-    if constexpr (LDS) {
-        if (ph * pw * CP > p.patch_cap) __builtin_trap();   // host sizing bug: never silently write past the patch
-        const int n = ph * pw * C;
-        for (int e = tid; e < n; e += kVisBlock) {
-            const int pc = e / C, ch = e - pc * C;
-            const int r = pc / pw, c = pc - r * pw;
-            s_patch[pc * CP + ch] = base[((int64_t)(r_lo + r) * p.w + c_lo + c) * p.ldx + ch];
-        }
-    }
+    tile.stage(p, s_patch, base);
     __syncthreads();
-    const int X = X0 + lane;
-    const bool xin = X < p.Wc;
-    const Lerp lw = lerp_src(xin ? X : X1, p.w, p.sw, p.align);
-    const int64_t pitch = LDS ? (int64_t)CP : p.ldx;
-    const int64_t o0 = (int64_t)(LDS ? lw.i0 - c_lo : lw.i0) * pitch, o1 = (int64_t)(LDS ? lw.i1 - c_lo : lw.i1) * pitch;
+    tile.set_lane(p, lane);
+    const int X = tile.X;
     const float* src = LDS ? s_patch : base;
-    const int64_t row_pitch = (LDS ? pw : p.w) * pitch;
     // the template arguments pp_acq_lowres_score_topk's launch takes for this C: strategy-specialised where the class count is
     // one of the datasets' and the patch is in LDS, the run-time strategy otherwise
     constexpr bool kSpec = EXACT && LDS;
@@ -110,16 +93,13 @@ __global__ __launch_bounds__(kVisBlock, 2) void vis_score_kernel(VisParams p)
     for (int q = 0; q < 4; ++q) { mn[q] = INFINITY; mx[q] = -INFINITY; }
 #pragma unroll 1
     for (int j = 0; j < p.ppt; ++j) {
-        const int Y = Y0 + wv * p.ppt + j;
-        if (Y < p.Hc && xin) {
-            const Lerp lh = lerp_src(Y, p.h, p.sh, p.align);
-            const float* r0 = src + (int64_t)(LDS ? lh.i0 - r_lo : lh.i0) * row_pitch;
-            const float* r1 = src + (int64_t)(LDS ? lh.i1 - r_lo : lh.i1) * row_pitch;
+        const int Y = tile.Y0 + wv * p.ppt + j;
+        if (Y < p.Hc && tile.xin) {
             float x[CMAX];
+            const auto tp = tile.taps(src, tile.row(p, Y));
 #pragma unroll
             for (int c = 0; c < CMAX; ++c)
-                if (EXACT || c < C)
-                    x[c] = bilerp(lh.l0, lh.l1, lw.l0, lw.l1, r0[o0 + c], r0[o1 + c], r1[o0 + c], r1[o1 + c]);
+                if (EXACT || c < C) x[c] = tp.at(c);
             float m = x[0];
             int am = 0;
 #pragma unroll
@@ -309,12 +289,7 @@ int pp_vis_lowres(const float* low, int64_t ldx, int64_t B, int64_t C, int64_t h
     p.panel_pred = p.panel_target + (target ? 1 : 0);
     p.n_rgb = p.panel_pred + 1;
 
-    // a tile of T output pixels spans at most ceil(scale*(T-1)) + 3 source pixels (i0 of the first .. i1 of the last)
-    auto patch_floats = [&](int ppt) {
-        const int64_t pw = std::min<int64_t>(w, (int64_t)std::ceil((double)p.sw * (kWave - 1)) + 3);
-        const int64_t ph = std::min<int64_t>(h, (int64_t)std::ceil((double)p.sh * (kVisWaves * ppt - 1)) + 3);
-        return ph * pw * (C | 1);
-    };
+    auto patch_floats = [&](int ppt) { return lowres_patch_floats(p.sh, p.sw, h, w, kVisWaves * ppt, C); };
     p.tiles_x = (int)cdiv(Wc, kWave);
     const int64_t tiles8 = p.tiles_x * cdiv(Hc, kVisWaves * 8);
     p.ppt = (B * tiles8 >= 256 && (size_t)patch_floats(8) * 4 <= kVisLdsSoft) ? 8 : 4;
@@ -327,14 +302,10 @@ int pp_vis_lowres(const float* low, int64_t ldx, int64_t B, int64_t C, int64_t h
 
     hipStream_t st = as_stream(stream);
     const dim3 grid((unsigned)(B * p.tiles_x * p.tiles_y));
-    switch (p.C) {
-        case 11: launch_vis_score<11, true>(p, lds, lds_bytes, grid, st); break;
-        case 19: launch_vis_score<19, true>(p, lds, lds_bytes, grid, st); break;
-        case 21: launch_vis_score<21, true>(p, lds, lds_bytes, grid, st); break;
-        default:
-            if (p.C <= 32) launch_vis_score<32, false>(p, lds, lds_bytes, grid, st);
-            else           launch_vis_score<64, false>(p, lds, lds_bytes, grid, st);
-    }
+    lowres_by_classes(C, [&](auto cmax, auto exact) {
+        launch_vis_score<decltype(cmax)::value, decltype(exact)::value>(p, lds, lds_bytes, grid, st);
+        return 0;
+    });
     if (int rc = check_launch("vis_score_kernel")) return rc;
     hipLaunchKernelGGL(vis_quant_kernel, dim3((unsigned)(B * p.quant_blocks)), dim3(kVisBlock), 0, st, p);
     return check_launch("vis_quant_kernel");

@@ -8,7 +8,7 @@ Check 2  against a float64 restatement in torch on the CPU (and, for the fixture
 Check 3  NaN entropy (0 * log 0): skipped by min / max, drawn 0, the other image of the batch untouched.
 Check 4  a head wider than 64 classes is refused.
 The shapes are the smallest that reach a second column tile, ragged right and bottom edges, the crop, both interpolation modes
-and per-image ranges."""
+and per-image ranges; G is the smallest down-sampling case whose patch does not fit the block's LDS."""
 import functools
 import os
 
@@ -31,6 +31,9 @@ SHAPES = {
     "C": (5, (20, 36), (40, 72), (37, 70), False, 2, 3.0, "cv", 5300),
     "D": (19, (16, 32), (64, 128), None, True, 3, 1.0, "cs", 5400),
     "E": (64, (6, 10), (24, 40), None, True, 1, 3.0, "cv", 5500),
+    # x1/2: a 16 x 64 tile interpolates from 33 x 129 source pixels, 323 KB at C = 19 - past the 48 KB a block stages, so every
+    # lane reads its four neighbours from memory (vis_score_kernel<..., LDS = false>); two tiles each way, both ragged
+    "G": (19, (40, 140), (20, 70), None, False, 1, 3.0, "cs", 5600),
 }
 
 
@@ -104,7 +107,7 @@ def restate64(c):
     return (top2[:, 0] - top2[:, 1]).numpy(), lg.argmax(dim=1).numpy(), torch.stack(qs, dim=1).numpy()
 
 
-ALL = ["A", "B", "C", "D", "E", "F"]
+ALL = ["A", "B", "C", "D", "E", "F", "G"]
 
 
 @pytest.mark.parametrize("name", ALL)
@@ -155,7 +158,7 @@ def _guarded_check(tag, got_gray, got_pred_rgb, palette, gap, am, q):
     assert np.array_equal(got_pred_rgb[sure], palette[am][sure])
 
 
-@pytest.mark.parametrize("name", ["A", "B", "C", "D", "E"])
+@pytest.mark.parametrize("name", ["A", "B", "C", "D", "E", "G"])
 def test_panels_against_float64(name):
     c, r = case(name), rendered(name)
     gap, am, q = restate64(c)

@@ -36,6 +36,9 @@ enum {
 
 /* query.py:229-239 UncertaintySampler strategies.  (`random`, query.py:242-244, is host RNG.) */
 enum { PP_ACQ_ENTROPY = 0, PP_ACQ_LEAST_CONFIDENCE = 1, PP_ACQ_MARGIN = 2 };
+/* Mutual information between the prediction and the dropout mask (BALD).  Valid ONLY at pp_acq_mean_prob_score_map and
+ * pp_acq_lowres_mc_mean_topk (below); every other entry keeps rejecting it as an unknown strategy. */
+enum { PP_ACQ_BALD = 3 };
 /* OR-ed into `strategy` at any acquisition entry point: score in the reference's OPERATION ORDER - p_c = exp(x_c - m) / S, then
  * sum(-p_c log p_c) with libm-accurate exp / log, each product and sum rounded separately (query.py:190,230) - instead of the default
  * algebraic form (entropy = log S + sum e_c (m - x_c) / S, v_exp_f32 exponentials; identical NaN behaviour).  Both forms are held to the
@@ -197,6 +200,41 @@ int pp_acq_vote_score_map(const uint8_t* votes, int64_t B, int64_t T, int64_t C,
 int pp_acq_lowres_mc_vote_topk(const float* low, int64_t ldx, int64_t B, int64_t T, int64_t C, int64_t h, int64_t w,
                                int64_t H, int64_t W, int align_corners, int64_t Hc, int64_t Wc,
                                const uint8_t* exclude, int strategy, int64_t k,
+                               int32_t* out_idx, float* out_val, float* out_map,
+                               void* workspace, size_t ws_bytes, pp_stream_t stream);
+
+/* MC-dropout scores of the MEAN PROBABILITY over the passes, and BALD.  The reference accumulates the mean probability
+ * (`prob += prob_`, query.py:185-187) but ranks pixels by the mean of the per-pass scores; the semantics below are this library's
+ * specification.  Per pixel, over T passes with logits x_t:
+ *   p_t = softmax(x_t)                       m = max_c x_c, S = sum_c expf(x_c - m), p_c = expf(x_c - m) / S (pp_acq_softmax_sum's)
+ *   pm_c = scale * sum_t p_t,c               fp32, ascending t, then one multiply: what pp_acq_softmax_sum writes to prob_out
+ *   PP_ACQ_ENTROPY / PP_ACQ_LEAST_CONFIDENCE / PP_ACQ_MARGIN   pp_uncertainty_from_prob's formulas on pm (the committee's consensus)
+ *   PP_ACQ_BALD    H(pm) - scale * sum_t H(p_t): the first term is the consensus entropy above, the second is what
+ *                  pp_acq_softmax_sum(..., uc_out, PP_ACQ_ENTROPY, scale, ...) writes; ONE IEEE subtraction, not clamped - rounding
+ *                  may leave the score of a deterministic pixel a few ulp below 0
+ * The largest scores win for entropy, least-confidence and BALD, the smallest for margin.  Excluded pixels get -1.0 (entropy,
+ * least-confidence, BALD) or 2.0 (margin), the hard vote's fills: 0.0 is the BALD of every deterministic pixel, and an excluded pixel
+ * sorts strictly behind those.  Ordering policy unchanged: value-sorted, ties -> lower flat index, NaN (0 * log 0 in a pass or in pm)
+ * first for largest; k beyond the number of un-excluded pixels returns excluded pixels, lowest index first.  PP_ACQ_REFERENCE_ORDER
+ * has no meaning here and is PP_ERR_BAD_ARG, as is any strategy above PP_ACQ_BALD.
+ *
+ * pp_acq_mean_prob_score_map - the tail of the full-size route: prob f32 [B,C,H,W] (element strides sB,sC,sH,sW; any class count)
+ * holds pm, mean_ent f32 [B,H,W] holds scale * sum_t H(p_t) - required for PP_ACQ_BALD, NULL otherwise (else PP_ERR_BAD_ARG) -,
+ * exclude u8 [B,H,W] or NULL -> out_map f32 [B,H,W].  Without exclusion the three consensus maps equal pp_uncertainty_from_prob's
+ * bit for bit.  Null prob / out_map, bad shape: PP_ERR_BAD_ARG; B > 65535: PP_ERR_UNSUPPORTED. */
+int pp_acq_mean_prob_score_map(const float* prob, int64_t B, int64_t C, int64_t H, int64_t W,
+                               int64_t sB, int64_t sC, int64_t sH, int64_t sW,
+                               const float* mean_ent, const uint8_t* exclude, int strategy, float* out_map, pp_stream_t stream);
+
+/* pp_acq_lowres_mc_score_topk with the scores above in place of the mean score: the passes, the consensus or BALD score, the fills
+ * and the top-k in one launch, no full-resolution logits of any pass and no [C,H,W] probability map.  Every argument, k == 0 (map
+ * only), the workspace pp_acq_lowres_workspace_bytes(B, C, Hc, Wc, k) and the error codes are that entry's; C <= 64
+ * (PP_ACQ_MAX_CLASSES), wider heads return PP_ERR_UNSUPPORTED (the full-size route serves them).  The result equals pp_bilinear_fwd
+ * of the B*T entries, pp_acq_softmax_sum(prob_out, uc_out with PP_ACQ_ENTROPY, accumulate = 0) per image,
+ * pp_acq_mean_prob_score_map and pp_topk_select, bit for bit (tested). */
+int pp_acq_lowres_mc_mean_topk(const float* low, int64_t ldx, int64_t B, int64_t T, int64_t C, int64_t h, int64_t w,
+                               int64_t H, int64_t W, int align_corners, int64_t Hc, int64_t Wc,
+                               const uint8_t* exclude, int strategy, float scale, int64_t k,
                                int32_t* out_idx, float* out_val, float* out_map,
                                void* workspace, size_t ws_bytes, pp_stream_t stream);
 

@@ -353,3 +353,73 @@ def vote_score_map(votes: torch.Tensor, n_passes: int, exclude, strategy: str) -
                                               strategy_id(strategy), omap.data_ptr(), _lib.current_stream_ptr(dev))
     _lib.check(rc, "pp_acq_vote_score_map")
     return omap
+
+
+# ---- MC-dropout scores of the MEAN PROBABILITY over the passes, and BALD (include/pixelpick_hip.h, pp_acq_mean_prob_score_map) ----
+# The consensus of the committee: entropy / least-confidence / margin of pm = mean_t softmax(x_t), and the mutual information
+# H(pm) - mean_t H(p_t).  A strategy table of its own: STRATEGY_ID stays closed, so every other entry keeps refusing "bald".
+# Excluded pixels get MEAN_FILL (the hard vote's fills): 0.0 is the BALD of every deterministic pixel.
+MEAN_STRATEGY_ID = {"entropy": 0, "least_confidence": 1, "margin_sampling": 2, "margin": 2, "bald": 3}
+MEAN_LARGEST = {"entropy": True, "least_confidence": True, "margin_sampling": False, "margin": False, "bald": True}
+MEAN_FILL = {"entropy": -1.0, "least_confidence": -1.0, "margin_sampling": 2.0, "margin": 2.0, "bald": -1.0}
+
+
+def mean_strategy_id(strategy: str) -> int:
+    try:
+        return MEAN_STRATEGY_ID[strategy]
+    except KeyError:
+        raise ValueError(f"no mean-probability scorer for query strategy {strategy!r} (kernels: {sorted(MEAN_STRATEGY_ID)})") from None
+
+
+def mc_mean_topk_lowres(low: torch.Tensor, n_passes: int, size, exclude, strategy: str, k: int, crop=None,
+                        align_corners: bool = True, return_map: bool = False
+                        ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """mc_score_topk_lowres with the score of the MEAN PROBABILITY over the n_passes passes (strategy "entropy",
+    "least_confidence", "margin_sampling") or their mutual information ("bald") in place of the mean score: passes, score,
+    MEAN_FILL at excluded pixels and top-k in one launch, no full-resolution logits and no [C,H,W] probability map.
+
+    low [B*n_passes,h,w,C] f32 channels-last on the GPU, image-major; exclude [B,crop_h,crop_w].  Returns (idx int32 [B,k],
+    val f32 [B,k], map f32 [B,crop_h,crop_w] | None); k == 0 -> (None, None, map)."""
+    sid = mean_strategy_id(strategy)
+    B, T, h, w, C, ldx, H, W, Hc, Wc = _mc_geom(low, n_passes, size, crop)
+    L = _lib.lib()
+    dev = low.device
+    ex = _exclude_u8(exclude, B, Hc, Wc, dev)
+    want_map = return_map or k == 0
+    idx = torch.empty((B, k), dtype=torch.int32, device=dev) if k else None
+    val = torch.empty((B, k), dtype=torch.float32, device=dev) if k else None
+    omap = torch.empty((B, Hc, Wc), dtype=torch.float32, device=dev) if want_map else None
+    ws = _ws(L.pp_acq_lowres_workspace_bytes(B, C, Hc, Wc, k), dev) if k else None
+    with torch.cuda.device(dev):
+        rc = L.pp_acq_lowres_mc_mean_topk(low.data_ptr(), ldx, B, T, C, h, w, H, W, int(bool(align_corners)), Hc, Wc,
+                                          ex.data_ptr() if ex is not None else None, sid, 1.0 / T, k,
+                                          idx.data_ptr() if k else None, val.data_ptr() if k else None,
+                                          omap.data_ptr() if omap is not None else None,
+                                          ws.data_ptr() if k else None, ws.numel() if k else 0, _lib.current_stream_ptr(dev))
+    _lib.check(rc, "pp_acq_lowres_mc_mean_topk")
+    return idx, val, omap
+
+
+def mean_prob_score_map(prob: torch.Tensor, mean_ent: Optional[torch.Tensor], exclude, strategy: str) -> torch.Tensor:
+    """The same scores from a GIVEN mean probability: prob [B,C,H,W] f32 on the GPU (any strides, any class count; what
+    mc_accumulate_ leaves in prob_out) and, for "bald" only, mean_ent [B,H,W] = the mean per-pass entropy (its uc_out with the
+    entropy strategy; None for the other strategies) -> f32 [B,H,W], MEAN_FILL at excluded pixels."""
+    sid = mean_strategy_id(strategy)
+    _require_cuda_f32(prob, "prob", 4)
+    B, C, H, W = prob.shape
+    dev = prob.device
+    if (strategy == "bald") != (mean_ent is not None):
+        raise ValueError("mean_ent is required for 'bald' and must be None for every other strategy")
+    if mean_ent is not None and (not isinstance(mean_ent, torch.Tensor) or tuple(mean_ent.shape) != (B, H, W) or not mean_ent.is_contiguous()
+                                 or mean_ent.dtype != torch.float32 or mean_ent.device != dev):
+        raise ValueError(f"mean_ent must be a contiguous float32 {(B, H, W)} tensor on prob's device")
+    ex = _exclude_u8(exclude, B, H, W, dev)
+    omap = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    sB, sC, sH, sW = prob.stride()
+    with torch.cuda.device(dev):
+        rc = _lib.lib().pp_acq_mean_prob_score_map(prob.data_ptr(), B, C, H, W, sB, sC, sH, sW,
+                                                   mean_ent.data_ptr() if mean_ent is not None else None,
+                                                   ex.data_ptr() if ex is not None else None, sid, omap.data_ptr(),
+                                                   _lib.current_stream_ptr(dev))
+    _lib.check(rc, "pp_acq_mean_prob_score_map")
+    return omap

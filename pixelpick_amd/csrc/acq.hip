@@ -983,6 +983,212 @@ __global__ __launch_bounds__(kBlock, 2) void acq_lowres_mc_vote_kernel(LowresVot
     }
 }
 
+// ---- MC-dropout: scores of the MEAN PROBABILITY over the passes, and BALD ----------------------------------------------------
+// p_c = scale * sum_t softmax(x_t)_c (fp32, ascending t, one multiply: softmax_sum_kernel's prob_out), then
+//   entropy / least-confidence / margin   pixel_score(p, from_prob = 1): pp_uncertainty_from_prob's formulas on the consensus
+//   PP_ACQ_BALD                           H(p) - scale * sum_t H(p_t): the second term is softmax_sum_kernel's uc_out for the entropy
+//                                         strategy; ONE subtraction, not clamped (rounding may leave it a few ulp below 0)
+// Excluded pixels get the hard vote's fills: 0.0 is the BALD of every deterministic pixel.
+__device__ __forceinline__ float mean_fill(int strategy) { return strategy != PP_ACQ_MARGIN ? -1.0f : 2.0f; }
+
+// psum: the per-class sums over the passes, hsum: the sum of the per-pass entropies (BALD only)
+template <int CMAX, bool EXACT>
+__device__ __forceinline__ float mean_prob_score(const float (&psum)[CMAX], int C, int strategy, float hsum, float scale)
+{
+#pragma clang fp contract(off)      // the mean entropy and the difference are rounded separately, as the two launches of the full-size route do
+    float pm[CMAX];
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) pm[c] = scale * psum[c];
+    if (strategy != PP_ACQ_BALD) return pixel_score<CMAX, EXACT>(pm, C, strategy, 1);
+    const float mean_ent = scale * hsum;
+    return pixel_score<CMAX, EXACT>(pm, C, PP_ACQ_ENTROPY, 1) - mean_ent;
+}
+
+// mc_pass_score's arithmetic with the class vector RE-READ for the maximum, the sum and the probabilities instead of held in
+// registers (that function's CMAX == 0 form: expf evaluated twice per class, the same value both times), but unrolled to CMAX with a
+// per-class predicate, so that on_prob(c, p_c) meets the caller's accumulators at constant indices.  Returns the pass's entropy (ENT).
+// The compiler barriers keep the three sweeps apart: merged, they are the register form again, with the class vector live beside
+// the accumulators.
+template <bool ENT, int CMAX, typename X, typename P>
+__device__ __forceinline__ float mc_pass_probs_streamed(X x, int C, P on_prob)
+{
+    float m = x(0);
+#pragma unroll
+    for (int c = 1; c < CMAX; ++c)
+        if (c < C) m = fmaxf(m, x(c));
+    asm volatile("" ::: "memory");
+    float S = 0.0f;
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c)
+        if (c < C) S += expf(x(c) - m);
+    asm volatile("" ::: "memory");
+    float ent = 0.0f;
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c)
+        if (c < C) {
+            const float pc = expf(x(c) - m) / S;
+            on_prob(c, pc);
+            if (ENT) ent = fmaf(-pc, logf(pc), ent);
+        }
+    return ent;
+}
+
+// acq_lowres_mc_kernel's tile (4 rows per wave) and selection tail with per-class accumulators.  Two loop orders:
+//   LDS   passes outer (the patch is staged once per pass), rows inner: 4 x CMAX accumulators per lane; CMAX <= 32
+//   !LDS  rows outer, passes inner, taps read from memory: CMAX accumulators per lane - the form of the <= 64 instantiation, whose
+//         4 x 64 accumulators would not fit the register file, and of every shape whose patch does not fit the LDS
+// Either way a pixel's sums grow in ascending t.  BALD: the per-pass entropy is kept as well (logf per class and pass); the
+// other three strategies run no logf in the pass loop.  The final formula's strategy is a run-time value.
+template <int CMAX, bool EXACT, bool LDS, bool BALD>
+__global__ __launch_bounds__(kBlock, 2) void acq_lowres_mc_mean_kernel(LowresMcParams q)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_patch[];
+    __shared__ uint64_t s_surv[kBlock / kWave][kSurvCap];
+    __shared__ uint32_t s_cnt[kBlock / kWave];
+    __shared__ uint64_t s_top[(kBlock / kWave) * kSmallKMax];
+    static_assert(!LDS || CMAX <= 32, "the LDS form keeps 4 x CMAX accumulators");
+    constexpr int PPT = 4;
+    constexpr int kPass = BALD ? PP_ACQ_ENTROPY : PP_ACQ_LEAST_CONFIDENCE;      // what mc_pass_score computes beside the probabilities
+    const LowresParams& p = q.g;
+    const int tiles = p.tiles_x * p.tiles_y;
+    const int img = blockIdx.x / tiles;
+    const int t = blockIdx.x - img * tiles;
+    const int ty = t / p.tiles_x, tx = t - ty * p.tiles_x;
+    const int tid = threadIdx.x, lane = tid & (kWave - 1);
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int C = EXACT ? CMAX : p.C;
+    const bool largest = p.strategy != PP_ACQ_MARGIN;
+    const float fill = mean_fill(p.strategy);
+    const int64_t N = (int64_t)p.Hc * p.Wc;
+    LowresTile<LDS> tile(p, C, tx, ty, (kBlock / kWave) * PPT, kBlock);
+    tile.set_lane(p, lane);
+    const int64_t pass_stride = (int64_t)p.h * p.w * p.ldx;
+    const float* img_base = p.low + (int64_t)img * q.T * pass_stride;
+    const uint8_t* excl = p.exclude ? p.exclude + (int64_t)img * N : nullptr;
+    float* omap = p.out_map ? p.out_map + (int64_t)img * N : nullptr;
+    uint32_t kh[PPT], kl[PPT];
+
+    if constexpr (LDS) {
+        float acc[PPT][CMAX], hs[PPT];
+#pragma unroll
+        for (int j = 0; j < PPT; ++j) {
+            hs[j] = 0.0f;
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c) acc[j][c] = 0.0f;
+        }
+        for (int ps = 0; ps < q.T; ++ps) {
+            const float* base = img_base + (int64_t)ps * pass_stride;
+            if (ps) __syncthreads();          // every wave has finished reading the previous pass's patch
+            // acq_lowres_mc_kernel's staging loop (the patch fits patch_cap by the host's lowres_patch_floats())
+            const int n = tile.ph * tile.pw * C;
+            for (int e = tid; e < n; e += kBlock) {
+                const int pc = e / C, ch = e - pc * C;
+                const int r = pc / tile.pw, c = pc - r * tile.pw;
+                s_patch[pc * (C | 1) + ch] = base[((int64_t)(tile.r_lo + r) * p.w + tile.c_lo + c) * p.ldx + ch];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < PPT; ++j) {
+                const int Y = tile.Y0 + wv * PPT + j;
+                if (Y < p.Hc && tile.xin) {
+                    float x[CMAX];
+                    const auto tp = tile.taps(s_patch, tile.row(p, Y));
+#pragma unroll
+                    for (int c = 0; c < CMAX; ++c)
+                        if (EXACT || c < C) x[c] = tp.at(c);
+                    const float e = mc_pass_score<kPass, CMAX, EXACT>([&](int c) { return x[c]; }, C, 0, [&](int c, float pc) { acc[j][c] += pc; });
+                    if (BALD) hs[j] += e;
+                }
+                __builtin_amdgcn_sched_barrier(0);   // one pixel's class vector live at a time
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < PPT; ++j) {
+            const int Y = tile.Y0 + wv * PPT + j;
+            if (Y < p.Hc && tile.xin) {
+                lowres_emit_key(mean_prob_score<CMAX, EXACT>(acc[j], C, p.strategy, hs[j], q.scale), (int64_t)Y * p.Wc + tile.X, largest, fill,
+                                excl, omap, nullptr, 0.0f, kh[j], kl[j]);
+            } else {
+                kh[j] = 0u; kl[j] = 0u;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < PPT; ++j) {
+            const int Y = tile.Y0 + wv * PPT + j;
+            if (Y < p.Hc && tile.xin) {
+                float acc[CMAX], hs = 0.0f;
+#pragma unroll
+                for (int c = 0; c < CMAX; ++c) acc[c] = 0.0f;
+                const Lerp lh = tile.row(p, Y);
+                for (int ps = 0; ps < q.T; ++ps) {
+                    const auto tp = tile.taps(img_base + (int64_t)ps * pass_stride, lh);
+                    float e;
+                    if constexpr (CMAX > 32) {      // 64 accumulators: no room for the class vector beside them
+                        e = mc_pass_probs_streamed<BALD, CMAX>([&](int c) { return tp.at(c); }, C, [&](int c, float pc) { acc[c] += pc; });
+                    } else {
+                        float x[CMAX];
+#pragma unroll
+                        for (int c = 0; c < CMAX; ++c)
+                            if (EXACT || c < C) x[c] = tp.at(c);
+                        e = mc_pass_score<kPass, CMAX, EXACT>([&](int c) { return x[c]; }, C, 0, [&](int c, float pc) { acc[c] += pc; });
+                    }
+                    if (BALD) hs += e;
+                }
+                lowres_emit_key(mean_prob_score<CMAX, EXACT>(acc, C, p.strategy, hs, q.scale), (int64_t)Y * p.Wc + tile.X, largest, fill, excl,
+                                omap, nullptr, 0.0f, kh[j], kl[j]);
+            } else {
+                kh[j] = 0u; kl[j] = 0u;
+            }
+            __builtin_amdgcn_sched_barrier(0);   // one pixel's accumulators live at a time
+        }
+    }
+    if (p.cand)
+        block_emit_topk<PPT>(kh, kl, p.k, p.cand + ((int64_t)img * tiles + t) * p.k, p.reduce_mode, s_surv, s_cnt, s_top);
+}
+
+// Full-size route, any class count and any strides: the same scores from a GIVEN mean probability prob [B,C,H,W] (what
+// softmax_sum_kernel's prob_out holds) and, for BALD, the mean per-pass entropy mean_ent [B,N] (its uc_out).  One thread per pixel
+// streams the classes in class order - pixel_score(from_prob = 1)'s operations, so the map equals pp_uncertainty_from_prob's bit
+// for bit at the class counts that entry scores from registers.
+struct MeanMapParams {
+    const float* prob;
+    const float* mean_ent;    // [B,N]: BALD only
+    const uint8_t* exclude;   // [B,N] or null
+    float* out_map;           // [B,N]
+    int64_t N, sB, sC, sH, sW;
+    int C, W, strategy;
+};
+
+__global__ __launch_bounds__(kBlock) void mean_prob_score_kernel(MeanMapParams p)
+{
+#pragma clang fp contract(off)      // as pixel_score
+    const int64_t pix = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (pix >= p.N) return;
+    const int64_t img = blockIdx.y, o = img * p.N + pix;
+    const int64_t hh = pix / p.W, ww = pix - hh * p.W;
+    const float* x = p.prob + img * p.sB + hh * p.sH + ww * p.sW;
+    float sc;
+    if (p.strategy == PP_ACQ_ENTROPY || p.strategy == PP_ACQ_BALD) {
+        float acc = 0.0f;
+        for (int c = 0; c < p.C; ++c) {
+            const float v = x[(int64_t)c * p.sC];
+            acc += (-v) * logf(v);
+        }
+        sc = p.strategy == PP_ACQ_BALD ? acc - p.mean_ent[o] : acc;
+    } else {
+        float t1 = -INFINITY, t2 = -INFINITY;
+        for (int c = 0; c < p.C; ++c) {
+            const float v = x[(int64_t)c * p.sC];
+            t2 = fmaxf(t2, fminf(t1, v));
+            t1 = fmaxf(t1, v);
+        }
+        sc = p.strategy == PP_ACQ_LEAST_CONFIDENCE ? 1.0f - t1 : fabsf(t1 - t2);
+    }
+    if (p.exclude && p.exclude[o]) sc = mean_fill(p.strategy);
+    p.out_map[o] = sc;
+}
+
 // Full-size route, any class count: votes u8 [C,N] (+)= the per-class vote counts of the T passes in logits [T,C,H,W] (element
 // strides).  One thread per pixel streams the classes with the running best and bumps ONE byte per pass.
 __global__ __launch_bounds__(kBlock) void vote_accumulate_kernel(const float* logits, int T, int C, int W, int64_t N, int64_t sT, int64_t sC,
@@ -2814,7 +3020,56 @@ static int dispatch_lowres_mc_vote(const LowresVoteParams& q, const LowresPlan& 
     return lowres_by_classes(q.g.C, [&](auto cmax, auto exact) { return launch_lowres_mc_vote<decltype(cmax)::value, decltype(exact)::value>(q, pl, B, st); });
 }
 
-// The body the three low-resolution *_topk entries share, after their own validation.  `launch` runs the entry's scorer with the
+// ---- MC-dropout mean-probability scores and BALD: host side ------------------------------------------------------------
+// The strategy of the two mean-probability entries: 0..2 and PP_ACQ_BALD, no PP_ACQ_REFERENCE_ORDER (there is one operation order)
+static int validate_mean_strategy(int strategy)
+{
+    if (strategy & PP_ACQ_REFERENCE_ORDER)
+        return fail(PP_ERR_BAD_ARG, "mean-probability scorer: PP_ACQ_REFERENCE_ORDER has no meaning here (strategy 0x%x)", strategy);
+    if (strategy < 0 || strategy > PP_ACQ_BALD) return fail(PP_ERR_BAD_ARG, "unknown strategy %d", strategy);
+    return PP_OK;
+}
+
+// The 4-row tile in every form (acq_lowres_mc_mean_kernel); heads wider than 32 classes read their taps from memory
+static LowresPlan make_lowres_mc_mean_plan(int64_t B, int64_t C, int64_t h, int64_t w, int64_t Hc, int64_t Wc, float sh, float sw)
+{
+    LowresPlan pl = make_lowres_plan(B, C, h, w, Hc, Wc, sh, sw, true);
+    if (C > 32) {
+        pl.lds = false;
+        pl.patch_cap = 0;
+        pl.lds_bytes = 0;
+    }
+    return pl;
+}
+
+template <int CMAX, bool EXACT>
+static int launch_lowres_mc_mean(const LowresMcParams& q, const LowresPlan& pl, int64_t B, hipStream_t st)
+{
+    EventScope ev(st);
+    if (pl.ppt != 4) return fail(PP_ERR_BAD_ARG, "mean-probability low-resolution scorer: plan with %d rows per wave", pl.ppt);
+    dim3 grid((unsigned)(B * pl.tiles_x * pl.tiles_y)), block(kBlock);
+    const bool bald = q.g.strategy == PP_ACQ_BALD;
+#define PP_MEAN(L, D) hipLaunchKernelGGL((acq_lowres_mc_mean_kernel<CMAX, EXACT, L, D>), grid, block, (L) ? pl.lds_bytes : 0, st, q)
+    if constexpr (CMAX <= 32) {
+        if (pl.lds) {
+            if (bald) PP_MEAN(true, true);
+            else PP_MEAN(true, false);
+            return check_launch("acq_lowres_mc_mean_kernel");
+        }
+    }
+    if (pl.lds) return fail(PP_ERR_BAD_ARG, "mean-probability low-resolution scorer: LDS patch planned for C=%d", q.g.C);
+    if (bald) PP_MEAN(false, true);
+    else PP_MEAN(false, false);
+#undef PP_MEAN
+    return check_launch("acq_lowres_mc_mean_kernel");
+}
+
+static int dispatch_lowres_mc_mean(const LowresMcParams& q, const LowresPlan& pl, int64_t B, hipStream_t st)
+{
+    return lowres_by_classes(q.g.C, [&](auto cmax, auto exact) { return launch_lowres_mc_mean<decltype(cmax)::value, decltype(exact)::value>(q, pl, B, st); });
+}
+
+// The body the four low-resolution *_topk entries share, after their own validation.  `launch` runs the entry's scorer with the
 // finished p (plan, map, candidate lists or histogram filled in): map only (k == 0); k <= 48: per-tile candidate lists + merge;
 // larger k: the score map (the caller's, or the workspace's) + the large-k selection on it at `qscale`, with the quantised
 // histogram counted by the scorer itself where the entry allows it (hist_ok).
@@ -3147,6 +3402,40 @@ int pp_acq_lowres_mc_vote_topk(const float* low, int64_t ldx, int64_t B, int64_t
     // k > 48: the map, then pp_topk_select's selection on it (qscale 0) - without the scorers' fused histogram, whose bins clamp the
     // fills (-1.0 / 2.0 lie outside the score range) into the end bins
     return run_lowres_select(q.g, pl, B, k, out_idx, out_val, workspace, ws_bytes, st, 0.0f, false, [&] { return dispatch_lowres_mc_vote(q, pl, B, st); });
+}
+
+int pp_acq_mean_prob_score_map(const float* prob, int64_t B, int64_t C, int64_t H, int64_t W, int64_t sB, int64_t sC, int64_t sH,
+                               int64_t sW, const float* mean_ent, const uint8_t* exclude, int strategy, float* out_map,
+                               pp_stream_t stream)
+{
+    if (!prob) return fail(PP_ERR_BAD_ARG, "mean_prob_score_map: prob is null");
+    if (!out_map) return fail(PP_ERR_BAD_ARG, "out_map is null");
+    if (int rc = validate_mean_strategy(strategy)) return rc;
+    if ((strategy == PP_ACQ_BALD) != (mean_ent != nullptr))
+        return fail(PP_ERR_BAD_ARG, "mean_prob_score_map: mean_ent is required for PP_ACQ_BALD and must be null otherwise (strategy %d)", strategy);
+    if (int rc = validate(prob, B, C, H, W, strategy == PP_ACQ_BALD ? PP_ACQ_ENTROPY : strategy)) return rc;
+    if (B > 65535) return fail(PP_ERR_UNSUPPORTED, "mean_prob_score_map: B=%lld > 65535 images per call", (long long)B);
+    MeanMapParams p{prob, mean_ent, exclude, out_map, H * W, sB, sC, sH, sW, (int)C, (int)W, strategy};
+    hipLaunchKernelGGL(mean_prob_score_kernel, dim3((unsigned)cdiv(p.N, kBlock), (unsigned)B), dim3(kBlock), 0, as_stream(stream), p);
+    return check_launch("mean_prob_score_kernel");
+}
+
+int pp_acq_lowres_mc_mean_topk(const float* low, int64_t ldx, int64_t B, int64_t T, int64_t C, int64_t h, int64_t w, int64_t H,
+                               int64_t W, int align_corners, int64_t Hc, int64_t Wc, const uint8_t* exclude, int strategy,
+                               float scale, int64_t k, int32_t* out_idx, float* out_val, float* out_map, void* workspace,
+                               size_t ws_bytes, pp_stream_t stream)
+{
+    if (!low) return fail(PP_ERR_BAD_ARG, "logits is null");
+    if (int rc = validate_mean_strategy(strategy)) return rc;
+    if (int rc = validate_lowres_mc(low, ldx, B, T, C, h, w, H, W, Hc, Wc, strategy == PP_ACQ_BALD ? PP_ACQ_ENTROPY : strategy)) return rc;
+    hipStream_t st = as_stream(stream);
+    float sh, sw;
+    lowres_scales(h, w, H, W, align_corners, sh, sw);
+    LowresMcParams q{{low, ldx, exclude, out_map, nullptr, (int)h, (int)w, (int)Hc, (int)Wc, sh, sw, align_corners ? 1 : 0,
+                      (int)C, 0, 0, 0, strategy, g_reduce_mode, 0}, (int)T, scale};
+    const LowresPlan pl = make_lowres_mc_mean_plan(B, C, h, w, Hc, Wc, sh, sw);
+    // k > 48: the map, then pp_topk_select's selection on it (qscale 0), as the hard vote: the fills lie outside the score range
+    return run_lowres_select(q.g, pl, B, k, out_idx, out_val, workspace, ws_bytes, st, 0.0f, false, [&] { return dispatch_lowres_mc_mean(q, pl, B, st); });
 }
 
 int pp_topk_select(const float* scores, int64_t B, int64_t N, int64_t k, int largest, int32_t* out_idx,

@@ -21,6 +21,12 @@ reference (`model.py:44,83`, `train.py:9,82`, `datasets/*.py` codecs) runs uncha
     stays that of the mean probability; the `random` strategy, rounds without MC-dropout and any other value ignore it.  The vote
     is specified on the logits pp_bilinear_fwd produces, i.e. for models that expose `forward_lowres` (on either route); a model
     without it keeps the mean score it had before (tests/test_acq_gpu.py pins those picks) and the round says so in a warning;
+  * `vote_type="consensus"` scores the strategy on the MEAN PROBABILITY of the passes (the `prob` the reference accumulates at
+    query.py:185-187 and only QueryStats reads), and `query_strategy="bald"` scores the mutual information H(mean p) - mean H(p_t)
+    (include/pixelpick_hip.h, pp_acq_mean_prob_score_map) - from the classifier output in one launch (pp_acq_lowres_mc_mean_topk)
+    or, on the full-size route (models without `forward_lowres`, chunked passes, heads wider than 64 classes), from the `prob` and
+    mean entropy pp_acq_softmax_sum accumulates + pp_acq_mean_prob_score_map + pp_topk_select: no model is left out.  "bald"
+    needs `use_mc_dropout` and is not a vote count: without MC-dropout, or with `vote_type="hard"`, it is a ValueError;
   * there is no CPU fallback: tensors must live on the GPU and the extension must be built.
 """
 import os
@@ -37,7 +43,7 @@ import torch.nn.functional as F
 from . import acquisition as acq
 from . import dist_utils
 
-_LARGEST_STRATEGIES = ("entropy", "least_confidence")
+_LARGEST_STRATEGIES = ("entropy", "least_confidence", "bald")
 # PIXELPICK_FUSED_LOWRES=0: always materialise the full-resolution logits (model(x)["pred"]) before scoring
 FUSED_LOWRES = os.environ.get("PIXELPICK_FUSED_LOWRES", "1") != "0"
 # PIXELPICK_QUERY_PIPELINE=0: finish every batch of an acquisition round (index / entropy read-back, masks, statistics)
@@ -73,6 +79,17 @@ class QuerySelector:
         # Default 8: identical picks (tested), 385 -> ~1500 images/s for an acquisition round on MI355X (tools/query_bench.py)
         self.query_batch_size = int(getattr(args, "query_batch_size", 8))
         self.mc_chunk = int(getattr(args, "mc_chunk", 32))     # stochastic passes per forward in the MC-dropout branch
+        self._check_bald()
+
+    def _check_bald(self):
+        """`bald` is the mutual information between the prediction and the dropout mask: it exists only over stochastic passes, and
+        it is a function of their probabilities, not of their votes.  Never a silent fall-back to another score."""
+        if self.query_strategy != "bald":
+            return
+        if not self.use_mc_dropout:
+            raise ValueError("query_strategy='bald' needs use_mc_dropout: a single deterministic pass has no mutual information")
+        if self.vote_type == "hard":
+            raise ValueError("query_strategy='bald' is scored from the passes' probabilities: it cannot be combined with vote_type='hard'")
 
     # ------------------------------------------------------------------ selection (query.py:33-69)
     @property
@@ -221,8 +238,12 @@ class QuerySelector:
         if self.use_mc_dropout:
             model.turn_on_dropout()
 
+        self._check_bald()
         print(f"Choosing pixels by {self.query_strategy}")
         is_random = self.query_strategy == "random"
+        is_bald = self.query_strategy == "bald"
+        # the strategy on the mean probability of the passes (vote_type="consensus"), or their mutual information ("bald")
+        mean_vote = self.use_mc_dropout and not is_random and (is_bald or self.vote_type == "consensus")
         records = []      # (image index, p_img, h, w, sorted flat indices int64, statistics contribution | None)
         y = None
         n_seen = 0
@@ -384,7 +405,7 @@ class QuerySelector:
                     h, w = it.size
                     excl_j = it.exclude | ~it.draws["cand"] if self.reverse_order else it.exclude
                     low, full_size = model.forward_lowres(it.x.expand(T, -1, -1, -1).contiguous())
-                    mc_topk = acq.mc_vote_topk_lowres if hard_vote else acq.mc_score_topk_lowres
+                    mc_topk = acq.mc_mean_topk_lowres if mean_vote else acq.mc_vote_topk_lowres if hard_vote else acq.mc_score_topk_lowres
                     idx, _, _ = mc_topk(low, T, full_size, torch.from_numpy(np.ascontiguousarray(excl_j))[None],
                                         self.query_strategy, self._k_launch(h, w), crop=(h, w), align_corners=lowres_align)
                     cand = choose(it, idx[0].cpu().numpy().astype(np.int64))[0]
@@ -411,8 +432,9 @@ class QuerySelector:
                         logits = self._forward_logits(model, it.x.expand(t, -1, -1, -1).contiguous(), h, w)
                         # uc_map += score(softmax(logits)) / n ; prob += softmax(logits) / n   (query.py:181-187), one HIP pass
                         # hard vote: the mean probability for the statistics as before, the votes of the chunk beside it
-                        soft_uc = None if is_random or hard_vote else uc_map
-                        acq.mc_accumulate_(logits, prob[0], soft_uc, self.query_strategy if soft_uc is not None else "entropy",
+                        # consensus: the mean probability alone; bald: the mean per-pass entropy beside it
+                        soft_uc = None if is_random or hard_vote or (mean_vote and not is_bald) else uc_map
+                        acq.mc_accumulate_(logits, prob[0], soft_uc, self.query_strategy if soft_uc is not None and not is_bald else "entropy",
                                            1.0 / self.mc_n_steps, accumulate=not first)
                         if hard_vote:
                             acq.mc_vote_accumulate_(logits, votes, accumulate=not first)
@@ -420,6 +442,10 @@ class QuerySelector:
                         first = False
                     if is_random:                       # the drawn map is already the mean of the mc_n_steps host draws
                         idx_sorted = self._random_topk(it.draws["rmap"][None], excl_j[None], self._k_launch(h, w))[0]
+                    elif mean_vote:
+                        uc_map = acq.mean_prob_score_map(prob, uc_map[None] if is_bald else None, excl_j[None], self.query_strategy)[0]
+                        idx_t, _ = acq.topk_select(uc_map.reshape(1, h * w), self._k_launch(h, w), self._largest)
+                        idx_sorted = idx_t[0].cpu().numpy().astype(np.int64)
                     elif hard_vote:
                         uc_map = acq.vote_score_map(votes, self.mc_n_steps, excl_j[None], self.query_strategy)[0]
                         idx_t, _ = acq.topk_select(uc_map.reshape(1, h * w), self._k_launch(h, w), self._largest)
@@ -577,6 +603,11 @@ class UncertaintySampler:
     @staticmethod
     def _margin_sampling(prob):
         return acq.uncertainty_from_prob(prob, "margin_sampling")
+
+    @staticmethod
+    def _bald(prob):
+        raise ValueError("'bald' is the mutual information over MC-dropout passes: a single prob has none "
+                         "(QuerySelector with use_mc_dropout, or acquisition.mean_prob_score_map with the mean per-pass entropy)")
 
     @staticmethod
     def _random(prob):

@@ -10,9 +10,14 @@ DeepLabv3+-MobileNetV2, 16 images of 256x512, 19 classes, entropy, device-synchr
   * --vote_type hard (args.py:34): the same two routes with the hard vote (pp_acq_lowres_mc_vote_topk / pp_acq_vote_accumulate +
     pp_acq_vote_score_map), the classifier-output route with the soft vote beside them, and the scorer call alone - the vote scorer
     next to the soft scorer at one image's shape (device events over `--scorer_calls` calls, `--repeats` blocks each, alternating;
-    the spread of the soft scorer's blocks is the run's own noise).
+    the spread of the soft scorer's blocks is the run's own noise);
+  * --vote_type consensus / --query_strategy bald: the scores of the mean probability and the mutual information
+    (pp_acq_lowres_mc_mean_topk / pp_acq_softmax_sum + pp_acq_mean_prob_score_map) on both routes, with TWO selectors of the soft
+    classifier-output route beside them in the same run: the ratio to the soft route is stated next to the difference between those
+    two, the run's own noise.  The 20 forwards dominate a round: no gain is expected or claimed.
 
-    python tools/mc_dropout_bench.py [--repeats 3] [--images 16] [--steps 20] [--chunks] [--only lowres|full] [--vote_type soft|hard]
+    python tools/mc_dropout_bench.py [--repeats 3] [--images 16] [--steps 20] [--chunks] [--only lowres|full]
+                                     [--vote_type soft|hard|consensus] [--query_strategy entropy|least_confidence|margin_sampling|bald]
                                      [--scorer_calls 200] [--out FILE]
 (--only: one route alone, for a kernel trace of it.)"""
 import argparse
@@ -93,7 +98,8 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--chunks", action="store_true")
     ap.add_argument("--only", choices=["lowres", "full"], default=None)
-    ap.add_argument("--vote_type", choices=["soft", "hard"], default="soft")
+    ap.add_argument("--vote_type", choices=["soft", "hard", "consensus"], default="soft")
+    ap.add_argument("--query_strategy", choices=["entropy", "least_confidence", "margin_sampling", "bald"], default="entropy")
     ap.add_argument("--scorer_calls", type=int, default=200)
     ap.add_argument("--out", default=None)
     o = ap.parse_args()
@@ -108,8 +114,8 @@ def main():
     with tempfile.TemporaryDirectory() as td:
         def selector(**kw):
             a = Namespace(dataset_name="cs", debug=False, dir_root=td, experim_name="mc", ignore_index=C, mc_n_steps=o.steps, n_classes=C,
-                          n_pixels_by_us=20, network_name="deeplab", weight_type="random", query_strategy="entropy", reverse_order=False,
-                          stride_total=16, top_n_percent=0.0, use_mc_dropout=True, mc_chunk=32, **dict(dict(vote_type=o.vote_type), **kw))
+                          n_pixels_by_us=20, network_name="deeplab", weight_type="random", reverse_order=False, stride_total=16, top_n_percent=0.0,
+                          use_mc_dropout=True, mc_chunk=32, **dict(dict(vote_type=o.vote_type, query_strategy=o.query_strategy), **kw))
             return ppq.QuerySelector(a, DL(DS(n)), device=torch.device("cuda:0"))
 
         routes = [("full-size route", False), ("classifier-output route", True)]
@@ -121,6 +127,14 @@ def main():
             if o.only != "full":
                 routes.append(("classifier-output route, soft vote", True))
                 sels.append(selector(vote_type="soft"))
+        mean_mode = o.vote_type == "consensus" or o.query_strategy == "bald"
+        if mean_mode:
+            mode = "BALD" if o.query_strategy == "bald" else f"consensus {o.query_strategy}"
+            routes = [(f"{name}, {mode}", fused) for name, fused in routes]
+            if o.only != "full":
+                for tag in ("a", "b"):
+                    routes.append((f"classifier-output route, soft vote ({tag})", True))
+                    sels.append(selector(vote_type="soft", query_strategy="entropy" if o.query_strategy == "bald" else o.query_strategy))
         times = [[] for _ in routes]
         for rep in range(o.repeats + 1):                       # round 0 of every route: warm-up
             for i, (_, fused) in enumerate(routes):
@@ -128,7 +142,7 @@ def main():
                 t = one_round(sels[i], model, rep + 1)
                 if rep:
                     times[i].append(t)
-        say(f"MC-dropout acquisition round, {n} images {h}x{w}, C={C}, mc_n_steps={o.steps}, vote_type={o.vote_type}, entropy, k=20; "
+        say(f"MC-dropout acquisition round, {n} images {h}x{w}, C={C}, mc_n_steps={o.steps}, vote_type={o.vote_type}, {o.query_strategy}, k=20; "
             f"{o.repeats} rounds per route, alternating")
         rates = []
         for (name, _), ts in zip(routes, times):
@@ -137,6 +151,10 @@ def main():
             say(f"  {name:48s} {np.mean(r):7.1f} images/s  (rounds: {', '.join(f'{x:.1f}' for x in r)}; spread {max(r) - min(r):.1f})")
         if len(rates) >= 2 and not o.only:
             say(f"  ratio to the full-size route: {np.mean(rates[1]) / np.mean(rates[0]):.2f}x")
+        if mean_mode and not o.only:
+            new, sa, sb = (float(np.mean(r)) for r in rates[1:4])
+            say(f"  classifier-output route, {mode} / soft vote: {new / ((sa + sb) / 2):.3f}  (the two soft selectors of this run: "
+                f"{sa:.1f} and {sb:.1f} images/s, {abs(sa - sb) / ((sa + sb) / 2) * 100:.1f} % apart); no pass/fail bar")
         if o.vote_type == "hard":
             scorer_times(o.steps, o.repeats, o.scorer_calls, say)
         if o.chunks:

@@ -238,6 +238,28 @@ int pp_acq_lowres_mc_mean_topk(const float* low, int64_t ldx, int64_t B, int64_t
                                int32_t* out_idx, float* out_val, float* out_map,
                                void* workspace, size_t ws_bytes, pp_stream_t stream);
 
+/* Spread-out picks: a minimum pixel distance between the picks of one image.  Stands beside query.py:57-64 - the top-k and the
+ * reference's only answer to clustered picks, a RANDOM sub-sample of the best top_n_percent - as a deterministic alternative; the
+ * semantics below are this library's specification.  Per image:
+ *   cand     i32 [B,M]: flat indices y*W + x in RANK order - what every *_topk entry writes to out_idx with k = M
+ *   W        the row length the flat indices were formed with; N the pixels per image (exclude's row length); 1 <= k <= M <= N
+ *   d        minimum distance in pixels, d >= 1;  exclude u8 [B,N] or NULL
+ *   spread phase  walk i = 0 .. M-1: skip cand[i] when exclude[cand[i]] != 0; accept it iff (y-y')^2 + (x-x')^2 >= d^2 for every
+ *                 pick (y',x') accepted so far (exact integer arithmetic, 64-bit where a coordinate difference can exceed 46340);
+ *                 stop at k accepted picks.  n = the number accepted.
+ *   fill phase    n < k: the remaining k - n slots take the earliest list positions the spread phase did not accept, in list order,
+ *                 the distance rule dropped (excluded candidates included) - k picks always come back, as from plain top-k.
+ *   out_idx  i32 [B,k] in acceptance order, then fill order;  out_pos i32 [B,k] the list position of each pick (to gather the
+ *            *_topk entry's out_val, or anything else kept per candidate);  out_n i32 [B] = n.
+ * d == 1 returns the first k un-excluded candidates.  A candidate outside [0, N) is treated as EXCLUDED: its exclusion byte is never
+ * read, the spread phase never accepts it, the fill phase may return it as it stands.
+ * One pick blocks at most A(d) = #{(dy,dx) : dy^2 + dx^2 < d^2} candidates, itself included, so with M = min(N, max(k, (k-1) A(d) + 1))
+ * the result equals the greedy pass over the image's whole ranking whenever the first M ranks hold no excluded pixel (tested).
+ * No workspace, no synchronisation.  k <= 1024 (the picks live in LDS), beyond: PP_ERR_UNSUPPORTED, as is B > 2^31 - 1.  Null cand /
+ * out_idx / out_pos / out_n, B / M / W / N / k / d < 1, k > M, M > N, N or W > 2^31 - 1: PP_ERR_BAD_ARG. */
+int pp_spread_select(const int32_t* cand, int64_t B, int64_t M, int64_t W, int64_t N, int64_t k, int64_t d,
+                     const uint8_t* exclude, int32_t* out_idx, int32_t* out_pos, int32_t* out_n, pp_stream_t stream);
+
 
 /* =============================================================================================
  * Network layers (DeepLabv3+-MobileNetV2 / FPN-ResNet50 forward + backward), NHWC fp32.

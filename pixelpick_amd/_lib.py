@@ -51,6 +51,7 @@ SIGNATURES = {
     "pp_acq_lowres_mc_vote_topk": (_int, [_p] + [_i64] * 8 + [_int, _i64, _i64, _p, _int, _i64, _p, _p, _p, _p, _sz, _p]),
     "pp_acq_mean_prob_score_map": (_int, [_p] + [_i64] * 8 + [_p, _p, _int, _p, _p]),
     "pp_acq_lowres_mc_mean_topk": (_int, [_p] + [_i64] * 8 + [_int, _i64, _i64, _p, _int, _f, _i64, _p, _p, _p, _p, _sz, _p]),
+    "pp_spread_select": (_int, [_p] + [_i64] * 6 + [_p, _p, _p, _p, _p]),
     "pp_conv2d_fwd_workspace_bytes": (_sz, [_int] * 10),
     "pp_conv2d_bwd_data_workspace_bytes": (_sz, [_int] * 10),
     "pp_conv2d_fwd": (_int, [_p, _i64, _int, _int, _int, _int, _p, _p, _int, _int, _int, _int, _int, _p, _i64, _int, _p, _sz, _p]),

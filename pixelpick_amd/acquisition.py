@@ -423,3 +423,72 @@ def mean_prob_score_map(prob: torch.Tensor, mean_ent: Optional[torch.Tensor], ex
                                                    _lib.current_stream_ptr(dev))
     _lib.check(rc, "pp_acq_mean_prob_score_map")
     return omap
+
+
+# ---- spread-out picks: a minimum pixel distance between the picks of one image (include/pixelpick_hip.h, pp_spread_select) ----
+SPREAD_MAX_PICKS = 1024        # the accepted picks live in LDS: more per image is PP_ERR_UNSUPPORTED
+
+
+def spread_reach(d: int) -> int:
+    """A(d) = #{(dy,dx) in Z^2 : dy^2 + dx^2 < d^2}: the candidates ONE pick can block at minimum distance d, itself included.
+    An exact count (integer arithmetic): A(1) = 1, A(2) = 9, A(8) = 193, A(16) = 793."""
+    d = int(d)
+    if d < 1:
+        raise ValueError(f"min_distance = {d}: must be >= 1")
+    from math import isqrt
+    # row dy holds the dx with dx^2 <= d^2 - 1 - dy^2
+    return sum(2 * isqrt(d * d - 1 - dy * dy) + 1 for dy in range(-(d - 1), d))
+
+
+def spread_candidates(k: int, d: int, N: int) -> int:
+    """M = min(N, max(k, (k-1) A(d) + 1)): among the first (k-1) A(d) + 1 un-excluded ranks there is always room for the k-th pick, so
+    the greedy pass over the top-M list equals the greedy pass over the whole ranking (as long as the first M ranks hold no excluded
+    pixel, i.e. at least M un-excluded pixels score strictly better than the exclusion fill)."""
+    k, N = int(k), int(N)
+    if k < 1 or N < 1:
+        raise ValueError(f"k = {k}, N = {N}: both must be >= 1")
+    return min(N, max(k, (k - 1) * spread_reach(d) + 1))
+
+
+def spread_select(cand: torch.Tensor, width: int, k: int, min_distance: int, exclude=None, n_pixels: Optional[int] = None
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Greedy minimum-distance selection (pp_spread_select): cand int32 [B,M] on the GPU, flat indices y*width + x in RANK order (the
+    idx of any *_topk function called with k = M).  Walks the list, skips excluded candidates, accepts one iff it lies >= min_distance
+    pixels from every pick accepted so far, stops at k; a list that ends first is topped up with its earliest unaccepted entries.
+    exclude: [B, ...] with n_pixels entries per image, or None; n_pixels defaults to exclude's entries per image (without a mask: no
+    bound on the indices is known, 2^31 - 1).  A candidate outside [0, n_pixels) counts as excluded.
+    Returns (idx int32 [B,k], pos int32 [B,k] = list position of each pick, n int32 [B] = picks that satisfy the distance rule)."""
+    if not isinstance(cand, torch.Tensor) or cand.ndim != 2 or cand.dtype != torch.int32:
+        raise ValueError("cand must be a 2-d int32 tensor [B,M]")
+    if not cand.is_cuda:
+        raise _lib.PixelPickHipError("cand must live on the GPU: the HIP path has no CPU fallback")
+    cand = cand.contiguous()
+    B, M = cand.shape
+    dev = cand.device
+    ex = None
+    if exclude is not None:
+        if isinstance(exclude, np.ndarray):
+            exclude = np.ascontiguousarray(exclude)
+        ex = torch.as_tensor(exclude)
+        if ex.shape[0] != B:
+            raise ValueError(f"exclude holds {ex.shape[0]} images, cand {B}")
+        if ex.dtype == torch.bool:
+            ex = ex.contiguous().view(torch.uint8)
+        elif ex.dtype != torch.uint8:
+            ex = (ex != 0).contiguous().view(torch.uint8)
+        ex = ex.to(dev, non_blocking=True).reshape(B, -1).contiguous()
+        if n_pixels is None:
+            n_pixels = ex.shape[1]
+        elif ex.shape[1] != int(n_pixels):
+            raise ValueError(f"exclude holds {ex.shape[1]} pixels per image, n_pixels = {n_pixels}")
+    N = 0x7FFFFFFF if n_pixels is None else int(n_pixels)
+    k = int(k)
+    idx = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+    pos = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+    n = torch.empty((B,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().pp_spread_select(cand.data_ptr(), B, M, int(width), N, k, int(min_distance),
+                                         ex.data_ptr() if ex is not None else None, idx.data_ptr(), pos.data_ptr(), n.data_ptr(),
+                                         _lib.current_stream_ptr(dev))
+    _lib.check(rc, "pp_spread_select")
+    return idx, pos, n

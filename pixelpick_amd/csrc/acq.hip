@@ -3112,6 +3112,113 @@ static int run_lowres_select(LowresParams& p, const LowresPlan& pl, int64_t B, i
     return run_large(map, B, N, k, largest, gbuf, out_idx, out_val, st, qscale, hist_ok);
 }
 
+// ---- pp_spread_select: greedy minimum-distance selection over a rank-ordered candidate list -----------------------------
+// One wave per image.  The accepted picks live in LDS as (y, x) pairs beside their list positions; the candidates are read 64 at a
+// time (coalesced, the chunk after next already in flight, the exclusion bytes of the next chunk beside it).  Each lane tests its
+// candidate against every pick accepted in earlier chunks (all lanes read the same LDS word: a broadcast); the survivors of the
+// chunk are then resolved in rank order - ballot, the lowest live lane is accepted, its coordinates are handed to the live lanes,
+// which drop out when they lie closer than d.  The wave leaves as soon as k picks are accepted; the fill phase is a second walk
+// and runs only when the list ended first.  WIDE: squared distances in 64 bits (a coordinate difference may exceed 46340);
+// otherwise H, W <= 32768 and 32 bits hold them.
+constexpr int kSpreadMaxK = 1024;
+
+struct SpreadParams {
+    const int32_t* cand;      // [B,M]
+    const uint8_t* exclude;   // [B,N] or null
+    int32_t* out_idx;         // [B,k]
+    int32_t* out_pos;         // [B,k]
+    int32_t* out_n;           // [B]
+    int64_t M, N;
+    uint64_t d2;              // d * d (d clamped to 2^31 on the host: every distance in an image of < 2^31 pixels is smaller)
+    int W, k;
+};
+
+template <bool WIDE>
+__device__ __forceinline__ bool spread_far(int y, int x, int py, int px, uint64_t d2)
+{
+    if constexpr (WIDE) {
+        const int64_t dy = (int64_t)y - py, dx = (int64_t)x - px;
+        return (uint64_t)(dy * dy) + (uint64_t)(dx * dx) >= d2;
+    } else {
+        const int dy = y - py, dx = x - px;
+        return (uint32_t)(dy * dy) + (uint32_t)(dx * dx) >= (uint32_t)d2;
+    }
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(kWave) void spread_select_kernel(SpreadParams p)
+{
+    __shared__ int2 s_pick[kSpreadMaxK];      // (y, x) of the accepted picks
+    __shared__ int s_pos[kSpreadMaxK];        // their list positions, ascending
+    const int lane = threadIdx.x;
+    const int64_t img = blockIdx.x;
+    const int32_t* cand = p.cand + img * p.M;
+    const uint8_t* excl = p.exclude ? p.exclude + img * p.N : nullptr;
+    int32_t* out_idx = p.out_idx + img * p.k;
+    int32_t* out_pos = p.out_pos + img * p.k;
+    const int64_t M = p.M;
+    const int k = p.k;
+    // a candidate outside [0, N) is treated as excluded: never accepted by the spread phase, its exclusion byte never read
+    auto load_c = [&](int64_t base) -> int { return base + lane < M ? cand[base + lane] : -1; };
+    auto load_e = [&](int c) -> int {
+        if (c < 0 || (int64_t)c >= p.N) return 1;
+        return excl ? (int)excl[c] : 0;
+    };
+    int n = 0;
+    int c0 = load_c(0), c1 = load_c(kWave);
+    int e0 = load_e(c0);
+    for (int64_t base = 0; base < M && n < k; base += kWave) {
+        const int c2 = load_c(base + 2 * kWave);
+        const int e1 = load_e(c1);
+        const int y = c0 / p.W, x = c0 - y * p.W;
+        bool alive = e0 == 0;                 // (beyond the list: c0 = -1, excluded)
+        for (int j = 0; j < n; ++j) {
+            const int2 q = s_pick[j];
+            alive = alive && spread_far<WIDE>(y, x, q.x, q.y, p.d2);
+        }
+        uint64_t live = __ballot(alive);
+        while (live != 0ull && n < k) {
+            const int l = __ffsll((long long)live) - 1;
+            const int py = __shfl(y, l, kWave), px = __shfl(x, l, kWave);
+            if (lane == l) {
+                s_pick[n] = make_int2(y, x);
+                s_pos[n] = (int)(base + lane);
+                out_idx[n] = c0;
+                out_pos[n] = (int)(base + lane);
+            }
+            alive = alive && spread_far<WIDE>(y, x, py, px, p.d2);      // lane l itself: distance 0 < d * d
+            live = __ballot(alive);
+            ++n;
+        }
+        __syncthreads();                      // one wave: orders the LDS writes above before the next chunk's reads
+        c0 = c1; e0 = e1; c1 = c2;
+    }
+    if (lane == 0) p.out_n[img] = n;
+    if (n == k) return;
+    // fill phase: the earliest list positions the spread phase did not accept, in list order, the distance rule dropped
+    int filled = n;
+    for (int64_t base = 0; base < M && filled < k; base += kWave) {
+        const int64_t i = base + lane;
+        bool take = i < M;
+        const int c = take ? cand[i] : 0;
+        if (take) {                           // accepted in the spread phase?  s_pos[0..n) ascends
+            int lo = 0, hi = n;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if ((int64_t)s_pos[mid] < i) lo = mid + 1; else hi = mid;
+            }
+            take = !(lo < n && (int64_t)s_pos[lo] == i);
+        }
+        const uint64_t m = __ballot(take);
+        const int slot = filled + __popcll(m & ((1ull << lane) - 1ull));
+        if (take && slot < k) {
+            out_idx[slot] = c;
+            out_pos[slot] = (int)i;
+        }
+        filled += __popcll(m);
+    }
+}
+
 }  // namespace pp
 
 using namespace pp;
@@ -3436,6 +3543,35 @@ int pp_acq_lowres_mc_mean_topk(const float* low, int64_t ldx, int64_t B, int64_t
     const LowresPlan pl = make_lowres_mc_mean_plan(B, C, h, w, Hc, Wc, sh, sw);
     // k > 48: the map, then pp_topk_select's selection on it (qscale 0), as the hard vote: the fills lie outside the score range
     return run_lowres_select(q.g, pl, B, k, out_idx, out_val, workspace, ws_bytes, st, 0.0f, false, [&] { return dispatch_lowres_mc_mean(q, pl, B, st); });
+}
+
+int pp_spread_select(const int32_t* cand, int64_t B, int64_t M, int64_t W, int64_t N, int64_t k, int64_t d, const uint8_t* exclude,
+                     int32_t* out_idx, int32_t* out_pos, int32_t* out_n, pp_stream_t stream)
+{
+    if (!cand) return fail(PP_ERR_BAD_ARG, "spread_select: cand is null");
+    if (!out_idx) return fail(PP_ERR_BAD_ARG, "spread_select: out_idx is null");
+    if (!out_pos) return fail(PP_ERR_BAD_ARG, "spread_select: out_pos is null");
+    if (!out_n) return fail(PP_ERR_BAD_ARG, "spread_select: out_n is null");
+    if (B < 1) return fail(PP_ERR_BAD_ARG, "spread_select: B=%lld < 1", (long long)B);
+    if (N < 1 || N > 0x7FFFFFFFll) return fail(PP_ERR_BAD_ARG, "spread_select: N=%lld outside [1, 2^31 - 1]", (long long)N);
+    if (W < 1 || W > 0x7FFFFFFFll) return fail(PP_ERR_BAD_ARG, "spread_select: W=%lld outside [1, 2^31 - 1]", (long long)W);
+    if (M < 1 || M > N) return fail(PP_ERR_BAD_ARG, "spread_select: M=%lld outside [1, N=%lld]", (long long)M, (long long)N);
+    if (k < 1 || k > M) return fail(PP_ERR_BAD_ARG, "spread_select: k=%lld outside [1, M=%lld]", (long long)k, (long long)M);
+    if (d < 1) return fail(PP_ERR_BAD_ARG, "spread_select: d=%lld < 1", (long long)d);
+    if (k > kSpreadMaxK) return fail(PP_ERR_UNSUPPORTED, "spread_select: k=%lld > %d picks per image", (long long)k, kSpreadMaxK);
+    if (B > 0x7FFFFFFFll) return fail(PP_ERR_UNSUPPORTED, "spread_select: B=%lld > 2^31 - 1 images per call", (long long)B);
+    const int64_t H = cdiv(N, W);
+    const bool wide = H > 32768 || W > 32768;
+    // no two pixels of an image are 2^31 apart: a larger d selects the same picks.  32-bit form: dy^2 + dx^2 < 2^31
+    uint64_t d2 = (uint64_t)(d < (1ll << 31) ? d : (1ll << 31));
+    d2 *= d2;
+    if (!wide && d2 > 0x80000000ull) d2 = 0x80000000ull;
+    SpreadParams p{cand, exclude, out_idx, out_pos, out_n, M, N, d2, (int)W, (int)k};
+    if (wide)
+        hipLaunchKernelGGL(spread_select_kernel<true>, dim3((unsigned)B), dim3(kWave), 0, as_stream(stream), p);
+    else
+        hipLaunchKernelGGL(spread_select_kernel<false>, dim3((unsigned)B), dim3(kWave), 0, as_stream(stream), p);
+    return check_launch("spread_select_kernel");
 }
 
 int pp_topk_select(const float* scores, int64_t B, int64_t N, int64_t k, int largest, int32_t* out_idx,

@@ -27,6 +27,12 @@ reference (`model.py:44,83`, `train.py:9,82`, `datasets/*.py` codecs) runs uncha
     or, on the full-size route (models without `forward_lowres`, chunked passes, heads wider than 64 classes), from the `prob` and
     mean entropy pp_acq_softmax_sum accumulates + pp_acq_mean_prob_score_map + pp_topk_select: no model is left out.  "bald"
     needs `use_mc_dropout` and is not a vote count: without MC-dropout, or with `vote_type="hard"`, it is a ValueError;
+  * `args.min_pixel_distance = d >= 2` (absent, 0 and 1: off, every path as before) spreads the picks of an image out: every scoring
+    route of a round launches with k = M = acquisition.spread_candidates(n_pixels_by_us, d, h*w) and hands its rank-ordered device
+    indices to pp_spread_select (include/pixelpick_hip.h), which walks them greedily and skips a candidate closer than d pixels to a
+    pick already taken - on the device, no RNG, equal to the greedy pass over the image's whole ranking.  It is the deterministic
+    alternative to the random sub-sample of the best `top_n_percent` (query.py:63-64) and refuses to be combined with it, with
+    `reverse_order` and with the `random` strategy;
   * there is no CPU fallback: tensors must live on the GPU and the extension must be built.
 """
 import os
@@ -79,7 +85,10 @@ class QuerySelector:
         # Default 8: identical picks (tested), 385 -> ~1500 images/s for an acquisition round on MI355X (tools/query_bench.py)
         self.query_batch_size = int(getattr(args, "query_batch_size", 8))
         self.mc_chunk = int(getattr(args, "mc_chunk", 32))     # stochastic passes per forward in the MC-dropout branch
+        # not in the reference: minimum distance in pixels between the picks of one image (pp_spread_select); 0 / 1 = off
+        self.min_pixel_distance = int(getattr(args, "min_pixel_distance", 0) or 0)
         self._check_bald()
+        self._check_spread()
 
     def _check_bald(self):
         """`bald` is the mutual information between the prediction and the dropout mask: it exists only over stochastic passes, and
@@ -90,6 +99,41 @@ class QuerySelector:
             raise ValueError("query_strategy='bald' needs use_mc_dropout: a single deterministic pass has no mutual information")
         if self.vote_type == "hard":
             raise ValueError("query_strategy='bald' is scored from the passes' probabilities: it cannot be combined with vote_type='hard'")
+
+    def _check_spread(self):
+        """`min_pixel_distance` is the deterministic answer to clustered picks; the reference's answers draw from the host RNG and
+        give up the ranking the greedy pass walks.  Never both at once, and never silently one of them."""
+        d = self.min_pixel_distance
+        if d < 0:
+            raise ValueError(f"min_pixel_distance = {d}: a distance in pixels (0 or 1 switch it off)")
+        if d < 2:
+            return
+        if self.top_n_percent > 0.:
+            raise ValueError(f"min_pixel_distance = {d} cannot be combined with top_n_percent = {self.top_n_percent}: the random "
+                             f"sub-sample of the best pixels and the distance rule are two answers to one question - pass top_n_percent = 0")
+        if self.reverse_order:
+            raise ValueError(f"min_pixel_distance = {d} cannot be combined with reverse_order: its candidate set is a random draw")
+        if self.query_strategy == "random":
+            raise ValueError(f"min_pixel_distance = {d} cannot be combined with query_strategy = 'random': there is no ranking to walk")
+        if self.n_pixels_by_us > acq.SPREAD_MAX_PICKS:
+            raise ValueError(f"min_pixel_distance = {d} selects at most {acq.SPREAD_MAX_PICKS} pixels per image: n_pixels_by_us = {self.n_pixels_by_us}")
+
+    @property
+    def _spread_on(self) -> bool:
+        return self.min_pixel_distance >= 2
+
+    def _excl_arg(self, excl: np.ndarray):
+        """The exclusion mask as a scoring call takes it.  With min_pixel_distance it is uploaded ONCE here: the scorer and
+        pp_spread_select read the same device bytes."""
+        t = torch.from_numpy(np.ascontiguousarray(excl))
+        return t.view(torch.uint8).to(self.device, non_blocking=True) if self._spread_on else t
+
+    def _spread(self, idx: torch.Tensor, excl_dev, h: int, w: int) -> torch.Tensor:
+        """idx int32 [n,M] on the device, rank-ordered (a *_topk launch at k = _k_launch) -> the picks of the round [n,n_pixels_by_us]:
+        unchanged without min_pixel_distance, else pp_spread_select's (still on the device, nothing read back in between)."""
+        if not self._spread_on:
+            return idx
+        return acq.spread_select(idx, w, self.n_pixels_by_us, self.min_pixel_distance, exclude=excl_dev, n_pixels=h * w)[0]
 
     # ------------------------------------------------------------------ selection (query.py:33-69)
     @property
@@ -223,6 +267,8 @@ class QuerySelector:
         return d
 
     def _k_launch(self, h: int, w: int) -> int:
+        if self._spread_on:        # the candidates the greedy pass may need (never with reverse_order / top_n_percent)
+            return acq.spread_candidates(self.n_pixels_by_us, self.min_pixel_distance, h * w)
         return self.n_pixels_by_us if self.reverse_order else self._k_topk(h, w)
 
     def __call__(self, nth_query, model, human_labels: bool = False):
@@ -239,6 +285,7 @@ class QuerySelector:
             model.turn_on_dropout()
 
         self._check_bald()
+        self._check_spread()
         print(f"Choosing pixels by {self.query_strategy}")
         is_random = self.query_strategy == "random"
         is_bald = self.query_strategy == "bald"
@@ -314,9 +361,10 @@ class QuerySelector:
             for it in pending:
                 it.x.record_stream(main)
             low, full_size = model.forward_lowres(xs)
-            k = self._k_topk(h, w)
-            idx, _, _ = acq.score_topk_lowres(low, full_size, excl_dev, self.query_strategy, k, crop=(h, w), align_corners=lowres_align)
-            n = len(pending)
+            idx, _, _ = acq.score_topk_lowres(low, full_size, excl_dev, self.query_strategy, self._k_launch(h, w), crop=(h, w),
+                                              align_corners=lowres_align)
+            idx = self._spread(idx, excl_dev, h, w)            # min_pixel_distance: [n,M] -> [n,n_pixels_by_us], on the device
+            n, k = idx.shape
             idx_host = torch.empty((n, k), dtype=torch.int32, pin_memory=True)
             idx_host.copy_(idx, non_blocking=True)
             ent_host = None
@@ -368,12 +416,14 @@ class QuerySelector:
                     # the forward above only feeds the statistics (the reference runs it too, query.py:190)
                     idx_h = self._random_topk(np.stack([it.draws["rmap"] for it in pending]), excl, self._k_launch(h, w))
                 elif fused:
-                    idx, _, _ = acq.score_topk_lowres(low, full_size, torch.from_numpy(excl), self.query_strategy,
+                    excl_t = self._excl_arg(excl)
+                    idx, _, _ = acq.score_topk_lowres(low, full_size, excl_t, self.query_strategy,
                                                       self._k_launch(h, w), crop=(h, w), align_corners=lowres_align)
-                    idx_h = idx.cpu().numpy().astype(np.int64)
+                    idx_h = self._spread(idx, excl_t, h, w).cpu().numpy().astype(np.int64)
                 else:
-                    idx, _, _ = acq.score_topk(lg, torch.from_numpy(excl), self.query_strategy, self._k_launch(h, w))
-                    idx_h = idx.cpu().numpy().astype(np.int64)
+                    excl_t = self._excl_arg(excl)
+                    idx, _, _ = acq.score_topk(lg, excl_t, self.query_strategy, self._k_launch(h, w))
+                    idx_h = self._spread(idx, excl_t, h, w).cpu().numpy().astype(np.int64)
                 chosen = [choose(it, idx_h[j])[0] for j, it in enumerate(pending)]
                 want_stats = (not human_labels) and all(it.y is not None for it in pending)
                 ent_all = None
@@ -406,9 +456,10 @@ class QuerySelector:
                     excl_j = it.exclude | ~it.draws["cand"] if self.reverse_order else it.exclude
                     low, full_size = model.forward_lowres(it.x.expand(T, -1, -1, -1).contiguous())
                     mc_topk = acq.mc_mean_topk_lowres if mean_vote else acq.mc_vote_topk_lowres if hard_vote else acq.mc_score_topk_lowres
-                    idx, _, _ = mc_topk(low, T, full_size, torch.from_numpy(np.ascontiguousarray(excl_j))[None],
+                    excl_t = self._excl_arg(excl_j)[None]
+                    idx, _, _ = mc_topk(low, T, full_size, excl_t,
                                         self.query_strategy, self._k_launch(h, w), crop=(h, w), align_corners=lowres_align)
-                    cand = choose(it, idx[0].cpu().numpy().astype(np.int64))[0]
+                    cand = choose(it, self._spread(idx, excl_t, h, w)[0].cpu().numpy().astype(np.int64))[0]
                     ent = None
                     if not human_labels and it.y is not None:
                         ent = acq.mc_score_at_lowres(low, T, full_size, np.zeros(len(cand), dtype=np.int32), cand, "entropy",
@@ -443,17 +494,20 @@ class QuerySelector:
                     if is_random:                       # the drawn map is already the mean of the mc_n_steps host draws
                         idx_sorted = self._random_topk(it.draws["rmap"][None], excl_j[None], self._k_launch(h, w))[0]
                     elif mean_vote:
-                        uc_map = acq.mean_prob_score_map(prob, uc_map[None] if is_bald else None, excl_j[None], self.query_strategy)[0]
+                        excl_t = self._excl_arg(excl_j)[None]
+                        uc_map = acq.mean_prob_score_map(prob, uc_map[None] if is_bald else None, excl_t, self.query_strategy)[0]
                         idx_t, _ = acq.topk_select(uc_map.reshape(1, h * w), self._k_launch(h, w), self._largest)
-                        idx_sorted = idx_t[0].cpu().numpy().astype(np.int64)
+                        idx_sorted = self._spread(idx_t, excl_t, h, w)[0].cpu().numpy().astype(np.int64)
                     elif hard_vote:
-                        uc_map = acq.vote_score_map(votes, self.mc_n_steps, excl_j[None], self.query_strategy)[0]
+                        excl_t = self._excl_arg(excl_j)[None]
+                        uc_map = acq.vote_score_map(votes, self.mc_n_steps, excl_t, self.query_strategy)[0]
                         idx_t, _ = acq.topk_select(uc_map.reshape(1, h * w), self._k_launch(h, w), self._largest)
-                        idx_sorted = idx_t[0].cpu().numpy().astype(np.int64)
+                        idx_sorted = self._spread(idx_t, excl_t, h, w)[0].cpu().numpy().astype(np.int64)
                     else:
-                        uc_map[torch.from_numpy(excl_j).to(self.device)] = 0.0 if self._largest else 1.0
+                        excl_t = torch.from_numpy(excl_j).to(self.device)
+                        uc_map[excl_t] = 0.0 if self._largest else 1.0
                         idx_t, _ = acq.topk_select(uc_map.reshape(1, h * w), self._k_launch(h, w), self._largest)
-                        idx_sorted = idx_t[0].cpu().numpy().astype(np.int64)
+                        idx_sorted = self._spread(idx_t, excl_t[None], h, w)[0].cpu().numpy().astype(np.int64)
                     cand = choose(it, idx_sorted)[0]
                     ent = None
                     if not human_labels and it.y is not None:
@@ -468,9 +522,9 @@ class QuerySelector:
                     if is_random:
                         idx_sorted = self._random_topk(it.draws["rmap"][None], excl_j[None], self._k_launch(h, w))[0]
                     else:
-                        idx_t, _, _ = acq.score_topk(logits, torch.from_numpy(np.ascontiguousarray(excl_j))[None],
-                                                     self.query_strategy, self._k_launch(h, w))
-                        idx_sorted = idx_t[0].cpu().numpy().astype(np.int64)
+                        excl_t = self._excl_arg(excl_j)[None]
+                        idx_t, _, _ = acq.score_topk(logits, excl_t, self.query_strategy, self._k_launch(h, w))
+                        idx_sorted = self._spread(idx_t, excl_t, h, w)[0].cpu().numpy().astype(np.int64)
                     cand = choose(it, idx_sorted)[0]
                     ent = None
                     if not human_labels and it.y is not None:

@@ -260,6 +260,40 @@ int pp_acq_lowres_mc_mean_topk(const float* low, int64_t ldx, int64_t B, int64_t
 int pp_spread_select(const int32_t* cand, int64_t B, int64_t M, int64_t W, int64_t N, int64_t k, int64_t d,
                      const uint8_t* exclude, int32_t* out_idx, int32_t* out_pos, int32_t* out_n, pp_stream_t stream);
 
+/* Region-aware acquisition: window impurity x window uncertainty ("region impurity and prediction uncertainty", Xie et al., CVPR 2022).
+ * The reference has no such score; the semantics below are this library's specification (tests/region_oracle.py restates them).
+ * Per image of H x W pixels and a radius r, 1 <= r <= 16, at the pixel (y, x):
+ *   window      Omega = {(y',x') : |y'-y| <= r, |x'-x| <= r, 0 <= y' < H, 0 <= x' < W}: clipped at the image border, never wrapped, never
+ *               reaching into the next image of the batch.  N = |Omega| = (clipped rows) * (clipped columns), 1 <= N <= (2r+1)^2 <= 1089.
+ *   counts      n_c = #{p in Omega : pred[p] == c}, c = 0 .. C-1; a byte >= C (pp_predict_lowres writes none) is counted in ONE extra
+ *               bin C, so no input indexes out of range.
+ *   impurity    exact in integers: tab[n] = llrint(n * ln(n) * 2^16) computed in double on the host, tab[0] = tab[1] = 0 (the largest
+ *               entry, tab[1089] = 499 082 426, fits 31 bits).  G = sum_c tab[n_c], D = tab[N] - G: an integer >= 0, and 0 exactly
+ *               where the window holds one label.  P = (float)D / (float)(N * 65536): one int -> float conversion (round to nearest
+ *               even), one correctly rounded fp32 division; this is ln N - (1/N) sum_c n_c ln n_c, the entropy of the window's labels.
+ *               The integer sum makes P independent of the order in which the window is visited.
+ *   uncertainty u[p] = flip ? 1.0f - unc[p] : unc[p];  U = (sum_{p in Omega} u[p]) / (float)N, the sum in fp32 in a fixed order (the
+ *               2r+1 columns of each window row left to right from the first, then the 2r+1 row sums top to bottom from the first;
+ *               positions outside the image enter as +0.0f), so the same input gives the same bits on every run.  A NaN in unc makes
+ *               NaN exactly the outputs whose window holds it and changes no other output (no running sums over floats).
+ *   score       mode 0: P * U (one fp32 multiplication), mode 1: P, mode 2: U.  The LARGEST score wins in every mode (flip = 1 turns
+ *               the margin, whose smallest value is the most uncertain, into 1 - margin).
+ *   exclusion   exclude[p] != 0 sets the output AT p to -1.0f (0.0 is the legitimate score of every pure window, the fill ranks
+ *               behind it); the excluded pixel still counts inside other pixels' windows.
+ * pp_acq_region_table_words(r) = (2r+1)^2 + 1, 0 for r outside [1,16].  pp_acq_region_table fills host_tab[0 .. words) on the HOST (no
+ * launch; null host_tab: PP_ERR_BAD_ARG, r outside [1,16]: PP_ERR_UNSUPPORTED); the caller copies it to the device once per radius and
+ * owns that copy, like every workspace here.
+ * pp_acq_region_score_map: pred u8 [B,H,W] (what pp_predict_lowres writes), unc f32 [B,H,W] (what pp_acq_lowres_score_topk writes with
+ * k == 0), tab the DEVICE copy of the table for this r, exclude u8 [B,H,W] or NULL, out_map f32 [B,H,W], fully overwritten.  unc may
+ * be NULL in mode 1; pred and tab may be NULL in mode 2.  One launch; no workspace, no atomics, no synchronisation.
+ * PP_ERR_BAD_ARG: mode outside 0..2, a null required pointer, B / H / W < 1, C outside [1,256].  PP_ERR_UNSUPPORTED: r outside [1,16],
+ * H*W > 2^31 - 1, a grid past 2^31 - 1 blocks (one block per 64 x 64 tile of an image).  Every refusal comes before anything is
+ * enqueued and no pointer is read. */
+size_t pp_acq_region_table_words(int64_t r);
+int pp_acq_region_table(int64_t r, uint32_t* host_tab);
+int pp_acq_region_score_map(const uint8_t* pred, const float* unc, int64_t B, int64_t C, int64_t H, int64_t W, int64_t r, int mode,
+                            int flip, const uint32_t* tab, const uint8_t* exclude, float* out_map, pp_stream_t stream);
+
 
 /* =============================================================================================
  * Network layers (DeepLabv3+-MobileNetV2 / FPN-ResNet50 forward + backward), NHWC fp32.

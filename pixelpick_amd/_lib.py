@@ -52,6 +52,9 @@ SIGNATURES = {
     "pp_acq_mean_prob_score_map": (_int, [_p] + [_i64] * 8 + [_p, _p, _int, _p, _p]),
     "pp_acq_lowres_mc_mean_topk": (_int, [_p] + [_i64] * 8 + [_int, _i64, _i64, _p, _int, _f, _i64, _p, _p, _p, _p, _sz, _p]),
     "pp_spread_select": (_int, [_p] + [_i64] * 6 + [_p, _p, _p, _p, _p]),
+    "pp_acq_region_table_words": (_sz, [_i64]),
+    "pp_acq_region_table": (_int, [_i64, _p]),
+    "pp_acq_region_score_map": (_int, [_p, _p] + [_i64] * 5 + [_int, _int, _p, _p, _p, _p]),
     "pp_conv2d_fwd_workspace_bytes": (_sz, [_int] * 10),
     "pp_conv2d_bwd_data_workspace_bytes": (_sz, [_int] * 10),
     "pp_conv2d_fwd": (_int, [_p, _i64, _int, _int, _int, _int, _p, _p, _int, _int, _int, _int, _int, _p, _i64, _int, _p, _sz, _p]),
@@ -250,7 +253,7 @@ def lib():
 # arguments) and re-issued from a tight loop.  Unlike a hipGraph the replay keeps the two-queue eager schedule (main stream +
 # weight-gradient stream, the all-reduce under the encoder backward) - profiles/r02_graph_replay.txt shows why the graph loses.
 _NOT_LAUNCHES = ("pp_version", "pp_last_error", "pp_bn_fused_capacity", "pp_bn_fused_rows_cached", "pp_set_comm_cu_reserve",
-                 "pp_get_comm_cu_reserve")
+                 "pp_get_comm_cu_reserve", "pp_acq_region_table_words", "pp_acq_region_table")
 
 
 def _is_launch(name: str) -> bool:

@@ -492,3 +492,83 @@ def spread_select(cand: torch.Tensor, width: int, k: int, min_distance: int, exc
                                          _lib.current_stream_ptr(dev))
     _lib.check(rc, "pp_spread_select")
     return idx, pos, n
+
+
+# ---- region-aware acquisition: window impurity x window uncertainty (include/pixelpick_hip.h, pp_acq_region_score_map) ----
+REGION_TILE = (64, 64)         # (TH, TW) of region_score_kernel: one block per tile of one image (csrc/acq.hip, kRegionTH / kRegionTW)
+REGION_MAX_RADIUS = 16
+REGION_MODE_ID = {"product": 0, "impurity": 1, "uncertainty": 2}
+REGION_FILL = -1.0             # at excluded pixels: 0.0 is the score of every pure window; the largest score wins in every mode
+_region_tables = {}
+
+
+def _region_radius(radius) -> int:
+    r = int(radius)
+    if r < 1 or r > REGION_MAX_RADIUS:
+        raise ValueError(f"radius = {radius} outside [1, {REGION_MAX_RADIUS}]")
+    return r
+
+
+def region_table(radius: int, device) -> torch.Tensor:
+    """tab[n] = llrint(n ln(n) 2^16), n = 0 .. (2r+1)^2, computed on the host by pp_acq_region_table: a uint32 tensor on `device`,
+    made once per (radius, device) and kept."""
+    r = _region_radius(radius)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.PixelPickHipError("region_table: the table is a device tensor: the HIP path has no CPU fallback")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (r, device.index)
+    tab = _region_tables.get(key)
+    if tab is None:
+        L = _lib.lib()
+        host = np.empty(L.pp_acq_region_table_words(r), dtype=np.uint32)
+        _lib.check(L.pp_acq_region_table(r, host.ctypes.data), "pp_acq_region_table")
+        tab = _region_tables[key] = torch.from_numpy(host).to(device)
+    return tab
+
+
+def region_score_map(pred: Optional[torch.Tensor], unc: Optional[torch.Tensor], radius: int, n_classes: int, exclude=None,
+                     mode: str = "product", flip: bool = False) -> torch.Tensor:
+    """Per pixel, over its (2 radius + 1)^2 window clipped at the image border: the entropy of the predicted labels P ("impurity"),
+    the mean U of unc ("uncertainty"; flip: of 1 - unc, for the margin) or P * U ("product") -> f32 [B,H,W], REGION_FILL at excluded
+    pixels, the LARGEST score wins (pp_acq_region_score_map; one launch).
+
+    pred uint8 [B,H,W] (predict_lowres), unc f32 [B,H,W] (score_topk_lowres with k = 0), both contiguous on the GPU; pred may be None
+    in mode "uncertainty", unc in mode "impurity".  n_classes in [1, 256]: a label >= n_classes counts in one extra bin."""
+    try:
+        mid = REGION_MODE_ID[mode]
+    except (KeyError, TypeError):
+        raise ValueError(f"unknown region mode {mode!r} (modes: {sorted(REGION_MODE_ID)})") from None
+    r = _region_radius(radius)
+    C = int(n_classes)
+    if C < 1 or C > 256:
+        raise ValueError(f"n_classes = {n_classes} outside [1, 256] (the labels are bytes)")
+    need_pred, need_unc = mid != 2, mid != 1
+    if (need_pred and pred is None) or (need_unc and unc is None):
+        raise ValueError(f"mode {mode!r} needs {'pred' if pred is None and need_pred else 'unc'}")
+    ref = pred if need_pred else unc
+    for t, name, dtype in ((pred, "pred", torch.uint8), (unc, "unc", torch.float32)):
+        if t is None or not (need_pred if name == "pred" else need_unc):
+            continue
+        if not isinstance(t, torch.Tensor) or t.ndim != 3:
+            raise ValueError(f"{name} must be a 3-d tensor [B,H,W]")
+        if not t.is_cuda:
+            raise _lib.PixelPickHipError(f"{name} must live on the GPU: the HIP path has no CPU fallback")
+        if t.dtype != dtype:
+            raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if t.shape != ref.shape or t.device != ref.device:
+            raise ValueError(f"pred {tuple(pred.shape)} on {pred.device} and unc {tuple(unc.shape)} on {unc.device} must agree")
+    B, H, W = ref.shape
+    dev = ref.device
+    ex = _exclude_u8(exclude, B, H, W, dev)
+    tab = region_table(r, dev) if need_pred else None
+    omap = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().pp_acq_region_score_map(pred.data_ptr() if need_pred else None, unc.data_ptr() if need_unc else None,
+                                                B, C, H, W, r, mid, int(bool(flip)), tab.data_ptr() if tab is not None else None,
+                                                ex.data_ptr() if ex is not None else None, omap.data_ptr(), _lib.current_stream_ptr(dev))
+    _lib.check(rc, "pp_acq_region_score_map")
+    return omap

@@ -3219,6 +3219,196 @@ __global__ __launch_bounds__(kWave) void spread_select_kernel(SpreadParams p)
     }
 }
 
+// ---- pp_acq_region_score_map: window impurity x window uncertainty (include/pixelpick_hip.h has the specification) -------
+// One block per kRegionTH x kRegionTW tile of one image.  The (TH+2r) x (TW+2r) patch of label bins (u16; kRegionOut flags a position
+// outside the image, nothing is clamped) and of u (0.0f outside: x + 0.0f == x, so the clipped window's sum is untouched) is staged
+// once, a patch row per wave at a time.
+// Window uncertainty: a separable pass.  A wave turns a patch row into its 64 row sums IN PLACE (lane l reads columns l .. l+2r and
+// then writes column l: the wave's loads are all issued before its store, and no other wave touches the row), then each output
+// sums 2r+1 of them; both sums run from their first term in a fixed order (no running sum: a NaN reaches exactly the windows that
+// hold it).
+// Impurity: the block's waves split the tile's rows; lane l of a wave owns column l and walks down its rows with the window's
+// class counts in cnt[wave][bin][lane] (32-bit bins: the bank is the lane, no two lanes share a word).  The first window of a wave
+// is built by 2r+1 row insertions; from then on a row leaves and a row enters, column by column as a PAIR: equal labels change
+// nothing (inside a region of one label the step touches no count at all), different labels are two updates of different bins whose
+// reads are in flight together.  Each update moves G = sum_c tab[n_c] by dtab[n] = tab[n+1] - tab[n] (exact integers, so the
+// order of the walk cannot show in the result).  Per pixel that is at most 2(2r+1) updates whatever C is; C only sizes the
+// counts, which the host fits into the CU's 160 KiB by the number of waves.
+constexpr int kRegionTH = 64, kRegionTW = kWave, kRegionMaxR = 16, kRegionMaxWaves = 4;
+constexpr size_t kRegionLdsMax = 160 * 1024;
+constexpr uint32_t kRegionOut = 0xFFFFu;
+
+struct RegionParams {
+    const uint8_t* pred;      // [B,H,W]   (null in mode 2)
+    const float* unc;         // [B,H,W]   (null in mode 1)
+    const uint32_t* tab;      // [(2r+1)^2 + 1]   (null in mode 2)
+    const uint8_t* exclude;   // [B,H,W] or null
+    float* out;               // [B,H,W]
+    int H, W, C, r, mode, flip, tiles_x, tiles_y, waves;
+};
+
+struct RegionLds {            // offsets in 32-bit words into the block's dynamic LDS
+    int cnt, tab, dtab, u, lab;
+    size_t bytes;
+};
+
+__host__ __device__ inline RegionLds region_lds(int C, int r, int mode, int waves)
+{
+    const int K = (2 * r + 1) * (2 * r + 1), PH = kRegionTH + 2 * r, PW = kRegionTW + 2 * r;
+    const bool want_p = mode != 2, want_u = mode != 1;
+    RegionLds l;
+    int o = 0;
+    l.cnt = o;  o += want_p ? waves * (C + 1) * kWave : 0;
+    l.tab = o;  o += want_p ? K + 1 : 0;
+    l.dtab = o; o += want_p ? K + 1 : 0;
+    l.u = o;    o += want_u ? PH * PW : 0;
+    l.lab = o;  o += want_p ? (PH * PW + 1) / 2 : 0;
+    l.bytes = (size_t)o * 4;
+    return l;
+}
+
+__global__ __launch_bounds__(kRegionMaxWaves * kWave) void region_score_kernel(RegionParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_region[];
+    const RegionLds l = region_lds(p.C, p.r, p.mode, p.waves);
+    const int r = p.r, D = 2 * r + 1, K = D * D, PH = kRegionTH + 2 * r, PW = kRegionTW + 2 * r;
+    const int H = p.H, W = p.W, C = p.C;
+    const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const bool want_p = p.mode != 2, want_u = p.mode != 1;
+    uint32_t* s_cnt = s_region + l.cnt;
+    uint32_t* s_tab = s_region + l.tab;
+    uint32_t* s_dtab = s_region + l.dtab;
+    float* s_u = reinterpret_cast<float*>(s_region + l.u);
+    uint16_t* s_lab = reinterpret_cast<uint16_t*>(s_region + l.lab);
+
+    int64_t t = blockIdx.x;
+    const int tx = (int)(t % p.tiles_x);
+    t /= p.tiles_x;
+    const int ty = (int)(t % p.tiles_y);
+    const int64_t img = (t / p.tiles_y) * ((int64_t)H * W);
+    const int y0 = ty * kRegionTH, x0 = tx * kRegionTW;
+
+    if (want_p) {
+        for (int i = tid; i < p.waves * (C + 1) * kWave; i += nthr) s_cnt[i] = 0u;
+        for (int i = tid; i <= K; i += nthr) {
+            const uint32_t v = p.tab[i];
+            s_tab[i] = v;
+            s_dtab[i] = i < K ? p.tab[i + 1] - v : 0u;
+        }
+    }
+    for (int pr = wave; pr < PH; pr += p.waves) {
+        const int gy = y0 - r + pr;
+        const bool row_in = gy >= 0 && gy < H;
+        for (int pc = lane; pc < PW; pc += kWave) {
+            const int gx = x0 - r + pc;
+            const bool inside = row_in && gx >= 0 && gx < W;
+            const int64_t g = img + (int64_t)gy * W + gx;
+            if (want_p) {
+                uint32_t b = kRegionOut;
+                if (inside) {
+                    const uint32_t v = p.pred[g];
+                    b = v < (uint32_t)C ? v : (uint32_t)C;       // a byte >= C: the one extra bin
+                }
+                s_lab[pr * PW + pc] = (uint16_t)b;
+            }
+            if (want_u) {
+                float u = 0.0f;
+                if (inside) {
+                    const float v = p.unc[g];
+                    u = p.flip ? 1.0f - v : v;
+                }
+                s_u[pr * PW + pc] = u;
+            }
+        }
+    }
+    __syncthreads();
+    if (want_u) {
+        for (int pr = wave; pr < PH; pr += p.waves) {          // row sums in place: see the note above
+            float* q = s_u + pr * PW + lane;
+            float s = q[0];
+            for (int j = 1; j < D; ++j) s += q[j];
+            q[0] = s;
+        }
+        __syncthreads();
+    }
+    // no barrier below: a wave whose rows lie under the image leaves here
+    const int rows = (kRegionTH + p.waves - 1) / p.waves;
+    const int t0 = wave * rows;
+    const int t1 = min(min(t0 + rows, kRegionTH), H - y0);
+    if (t0 >= t1) return;
+    const int x = x0 + lane;
+    uint32_t* cnt = s_cnt + wave * (C + 1) * kWave + lane;
+    uint32_t G = 0u;                                           // sum_c tab[n_c] of this lane's window
+    // patch columns lane .. lane + 2r are the image columns x - r .. x + r; the next label is read while this one updates its count
+    auto add_row = [&](int pr) {
+        const uint16_t* q = s_lab + pr * PW + lane;
+        uint32_t b = q[0];
+        for (int j = 0; j < D; ++j) {
+            const uint32_t bn = q[min(j + 1, D - 1)];
+            if (b != kRegionOut) {
+                uint32_t* c = cnt + b * kWave;
+                const uint32_t n = *c;
+                G += s_dtab[n];
+                *c = n + 1u;
+            }
+            b = bn;
+        }
+    };
+    auto slide = [&](int pl, int pe) {                         // patch row pl leaves the window, patch row pe enters it
+        const uint16_t* ql = s_lab + pl * PW + lane;
+        const uint16_t* qe = s_lab + pe * PW + lane;
+        uint32_t bl = ql[0], be = qe[0];
+        for (int j = 0; j < D; ++j) {
+            const int jn = min(j + 1, D - 1);
+            const uint32_t bln = ql[jn], ben = qe[jn];
+            if (bl != be) {                                    // the same label (or both outside): counts and G stay
+                if (bl != kRegionOut && be != kRegionOut) {    // two different bins: both reads in flight together
+                    uint32_t* cl = cnt + bl * kWave;
+                    uint32_t* ce = cnt + be * kWave;
+                    const uint32_t nl = *cl - 1u, ne = *ce;
+                    G += s_dtab[ne] - s_dtab[nl];
+                    *cl = nl;
+                    *ce = ne + 1u;
+                } else if (bl != kRegionOut) {
+                    uint32_t* cl = cnt + bl * kWave;
+                    const uint32_t nl = *cl - 1u;
+                    G -= s_dtab[nl];
+                    *cl = nl;
+                } else {
+                    uint32_t* ce = cnt + be * kWave;
+                    const uint32_t ne = *ce;
+                    G += s_dtab[ne];
+                    *ce = ne + 1u;
+                }
+            }
+            bl = bln;
+            be = ben;
+        }
+    };
+    if (want_p)
+        for (int pr = t0; pr <= t0 + 2 * r; ++pr) add_row(pr);
+    for (int tr = t0; tr < t1; ++tr) {                         // output row y0 + tr: its window is patch rows tr .. tr + 2r
+        const int y = y0 + tr;
+        if (x < W) {
+            const int ny = min(y + r, H - 1) - max(y - r, 0) + 1, nx = min(x + r, W - 1) - max(x - r, 0) + 1;
+            const int N = ny * nx;
+            float P = 0.0f, U = 0.0f;
+            if (want_p) P = __fdiv_rn((float)(s_tab[N] - G), (float)(N << 16));
+            if (want_u) {
+                const float* q = s_u + tr * PW + lane;
+                float s = q[0];
+                for (int i = 1; i < D; ++i) s += q[i * PW];
+                U = __fdiv_rn(s, (float)N);
+            }
+            float v = p.mode == 0 ? __fmul_rn(P, U) : p.mode == 1 ? P : U;
+            const int64_t g = img + (int64_t)y * W + x;
+            if (p.exclude && p.exclude[g] != 0) v = -1.0f;
+            p.out[g] = v;
+        }
+        if (want_p && tr + 1 < t1) slide(tr, tr + 2 * r + 1);
+    }
+}
+
 }  // namespace pp
 
 using namespace pp;
@@ -3572,6 +3762,54 @@ int pp_spread_select(const int32_t* cand, int64_t B, int64_t M, int64_t W, int64
     else
         hipLaunchKernelGGL(spread_select_kernel<false>, dim3((unsigned)B), dim3(kWave), 0, as_stream(stream), p);
     return check_launch("spread_select_kernel");
+}
+
+size_t pp_acq_region_table_words(int64_t r)
+{
+    return r < 1 || r > kRegionMaxR ? 0 : (size_t)((2 * r + 1) * (2 * r + 1) + 1);
+}
+
+int pp_acq_region_table(int64_t r, uint32_t* host_tab)
+{
+    if (!host_tab) return fail(PP_ERR_BAD_ARG, "region_table: host_tab is null");
+    if (r < 1 || r > kRegionMaxR) return fail(PP_ERR_UNSUPPORTED, "region_table: r=%lld outside [1, %d]", (long long)r, kRegionMaxR);
+    const int64_t K = (2 * r + 1) * (2 * r + 1);
+    host_tab[0] = host_tab[1] = 0u;
+    for (int64_t n = 2; n <= K; ++n) host_tab[n] = (uint32_t)llrint((double)n * log((double)n) * 65536.0);
+    return PP_OK;
+}
+
+int pp_acq_region_score_map(const uint8_t* pred, const float* unc, int64_t B, int64_t C, int64_t H, int64_t W, int64_t r, int mode,
+                            int flip, const uint32_t* tab, const uint8_t* exclude, float* out_map, pp_stream_t stream)
+{
+    if (mode < 0 || mode > 2) return fail(PP_ERR_BAD_ARG, "region_score_map: mode=%d outside 0..2", mode);
+    if (!out_map) return fail(PP_ERR_BAD_ARG, "region_score_map: out_map is null");
+    if (mode != 2 && !pred) return fail(PP_ERR_BAD_ARG, "region_score_map: pred is null (mode %d)", mode);
+    if (mode != 2 && !tab) return fail(PP_ERR_BAD_ARG, "region_score_map: tab is null (mode %d)", mode);
+    if (mode != 1 && !unc) return fail(PP_ERR_BAD_ARG, "region_score_map: unc is null (mode %d)", mode);
+    if (B < 1) return fail(PP_ERR_BAD_ARG, "region_score_map: B=%lld < 1", (long long)B);
+    if (H < 1) return fail(PP_ERR_BAD_ARG, "region_score_map: H=%lld < 1", (long long)H);
+    if (W < 1) return fail(PP_ERR_BAD_ARG, "region_score_map: W=%lld < 1", (long long)W);
+    if (C < 1 || C > 256) return fail(PP_ERR_BAD_ARG, "region_score_map: C=%lld outside [1, 256] (labels are bytes)", (long long)C);
+    if (r < 1 || r > kRegionMaxR) return fail(PP_ERR_UNSUPPORTED, "region_score_map: r=%lld outside [1, %d]", (long long)r, kRegionMaxR);
+    const int64_t i31 = 0x7FFFFFFFll;
+    if (H > i31 / W) return fail(PP_ERR_UNSUPPORTED, "region_score_map: H*W=%lldx%lld > 2^31 - 1 pixels per image", (long long)H, (long long)W);
+    const int64_t tiles_x = cdiv(W, kRegionTW), tiles_y = cdiv(H, kRegionTH);
+    if (B > i31 / (tiles_x * tiles_y))
+        return fail(PP_ERR_UNSUPPORTED, "region_score_map: B=%lld images of %lld tiles: a grid past 2^31 - 1 blocks", (long long)B,
+                    (long long)(tiles_x * tiles_y));
+    // the class counts take (C+1) * 256 B per wave: as many waves as fit beside the patch (C = 256, r = 16: one wave, 127 KiB)
+    int waves = kRegionMaxWaves;
+    while (waves > 1 && region_lds((int)C, (int)r, mode, waves).bytes > kRegionLdsMax) waves /= 2;
+    const size_t lds_bytes = region_lds((int)C, (int)r, mode, waves).bytes;
+    if (lds_bytes > kRegionLdsMax) return fail(PP_ERR_UNSUPPORTED, "region_score_map: %zu bytes of LDS", lds_bytes);
+    if (lds_bytes > 64 * 1024) {                      // beyond the default dynamic-LDS limit of a launch: raise this kernel's (sticky, no sync)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(region_score_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        (void)hipGetLastError();
+    }
+    RegionParams p{pred, unc, tab, exclude, out_map, (int)H, (int)W, (int)C, (int)r, mode, flip ? 1 : 0, (int)tiles_x, (int)tiles_y, waves};
+    hipLaunchKernelGGL(region_score_kernel, dim3((unsigned)(B * tiles_x * tiles_y)), dim3(waves * kWave), lds_bytes, as_stream(stream), p);
+    return check_launch("region_score_kernel");
 }
 
 int pp_topk_select(const float* scores, int64_t B, int64_t N, int64_t k, int largest, int32_t* out_idx,

@@ -33,6 +33,16 @@ reference (`model.py:44,83`, `train.py:9,82`, `datasets/*.py` codecs) runs uncha
     pick already taken - on the device, no RNG, equal to the greedy pass over the image's whole ranking.  It is the deterministic
     alternative to the random sub-sample of the best `top_n_percent` (query.py:63-64) and refuses to be combined with it, with
     `reverse_order` and with the `random` strategy;
+  * `args.region_radius = r` in [1, 16] (absent or 0: off, every path as before) ranks a pixel by its (2r+1)^2 neighbourhood instead of
+    its own class vector: the entropy of the predicted labels in the window times the window mean of the configured strategy's
+    uncertainty ("region impurity and prediction uncertainty"; `args.region_mode` = "product" (default) | "impurity" |
+    "uncertainty"; include/pixelpick_hip.h, pp_acq_region_score_map).  The two scoring branches that hold the classifier output -
+    the pipelined batch and the fused batch - then run pp_predict_lowres (label map), pp_acq_lowres_score_topk with k = 0 (score
+    map), pp_acq_region_score_map (the mask applied there; `margin_sampling` enters as 1 - margin, the largest score wins) and
+    pp_topk_select, all on the device with nothing new read back; `top_n_percent`, `reverse_order` and `min_pixel_distance` work
+    on its ranking as on any other.  Out of scope and REFUSED with a ValueError, never a silent fall-back: the MC-dropout routes
+    (`use_mc_dropout`, "bald"), the `random` strategy, heads wider than 256 classes and the full-size route (a model without
+    `forward_lowres`, FUSED_LOWRES switched off);
   * there is no CPU fallback: tensors must live on the GPU and the extension must be built.
 """
 import os
@@ -47,6 +57,7 @@ import torch
 import torch.nn.functional as F
 
 from . import acquisition as acq
+from .predict import predict_lowres
 from . import dist_utils
 
 _LARGEST_STRATEGIES = ("entropy", "least_confidence", "bald")
@@ -87,8 +98,12 @@ class QuerySelector:
         self.mc_chunk = int(getattr(args, "mc_chunk", 32))     # stochastic passes per forward in the MC-dropout branch
         # not in the reference: minimum distance in pixels between the picks of one image (pp_spread_select); 0 / 1 = off
         self.min_pixel_distance = int(getattr(args, "min_pixel_distance", 0) or 0)
+        # not in the reference: score a pixel by its (2r+1)^2 window (pp_acq_region_score_map); 0 = off
+        self.region_radius = int(getattr(args, "region_radius", 0) or 0)
+        self.region_mode = getattr(args, "region_mode", None) or "product"
         self._check_bald()
         self._check_spread()
+        self._check_region()
 
     def _check_bald(self):
         """`bald` is the mutual information between the prediction and the dropout mask: it exists only over stochastic passes, and
@@ -122,11 +137,48 @@ class QuerySelector:
     def _spread_on(self) -> bool:
         return self.min_pixel_distance >= 2
 
+    def _check_region(self, model=None):
+        """`region_radius` scores from the single-pass classifier output only; everything else is refused by name, never replaced by
+        the per-pixel score.  With a model (at the round): it must expose forward_lowres."""
+        r = self.region_radius
+        if r == 0:
+            return
+        if r < 1 or r > acq.REGION_MAX_RADIUS:
+            raise ValueError(f"region_radius = {r} outside [1, {acq.REGION_MAX_RADIUS}] (0 switches it off)")
+        if self.region_mode not in acq.REGION_MODE_ID:
+            raise ValueError(f"region_radius = {r}: unknown region_mode {self.region_mode!r} (modes: {sorted(acq.REGION_MODE_ID)})")
+        if self.query_strategy in ("random", "bald"):
+            raise ValueError(f"region_radius = {r} cannot be combined with query_strategy = {self.query_strategy!r}: the window "
+                             f"uncertainty is the mean of a single-pass score map (entropy, least_confidence, margin_sampling)")
+        if self.use_mc_dropout:
+            raise ValueError(f"region_radius = {r} cannot be combined with use_mc_dropout: the MC-dropout routes are not region-scored")
+        if self.n_classes > 256:
+            raise ValueError(f"region_radius = {r} needs a label map of bytes: n_classes = {self.n_classes} > 256")
+        if model is not None and not (FUSED_LOWRES and hasattr(model, "forward_lowres")):
+            raise ValueError(f"region_radius = {r} is scored from the classifier output: the model needs forward_lowres (and FUSED_LOWRES "
+                             f"on); the full-size route is not region-scored")
+
+    @property
+    def _region_on(self) -> bool:
+        return self.region_radius >= 1
+
+    def _region_topk(self, low, full_size, excl_dev, h: int, w: int, align: bool) -> torch.Tensor:
+        """The region-scored replacement of one score_topk_lowres launch: label map + score map of the configured strategy (no mask) ->
+        window impurity x window uncertainty with the mask applied -> top-k, the largest first.  int32 [n,_k_launch] on the device."""
+        C = int(low.shape[-1])
+        if C > 256:
+            raise ValueError(f"region_radius = {self.region_radius} needs a label map of bytes: the model has {C} classes")
+        pred, _ = predict_lowres(low, full_size, crop=(h, w), align_corners=align, want_pred=True)
+        _, _, unc = acq.score_topk_lowres(low, full_size, None, self.query_strategy, 0, crop=(h, w), align_corners=align)
+        rmap = acq.region_score_map(pred, unc, self.region_radius, C, exclude=excl_dev, mode=self.region_mode,
+                                    flip=not acq.LARGEST[self.query_strategy])
+        return acq.topk_select(rmap.reshape(rmap.shape[0], h * w), self._k_launch(h, w), True)[0]
+
     def _excl_arg(self, excl: np.ndarray):
         """The exclusion mask as a scoring call takes it.  With min_pixel_distance it is uploaded ONCE here: the scorer and
         pp_spread_select read the same device bytes."""
         t = torch.from_numpy(np.ascontiguousarray(excl))
-        return t.view(torch.uint8).to(self.device, non_blocking=True) if self._spread_on else t
+        return t.view(torch.uint8).to(self.device, non_blocking=True) if self._spread_on or self._region_on else t
 
     def _spread(self, idx: torch.Tensor, excl_dev, h: int, w: int) -> torch.Tensor:
         """idx int32 [n,M] on the device, rank-ordered (a *_topk launch at k = _k_launch) -> the picks of the round [n,n_pixels_by_us]:
@@ -286,6 +338,7 @@ class QuerySelector:
 
         self._check_bald()
         self._check_spread()
+        self._check_region(model)
         print(f"Choosing pixels by {self.query_strategy}")
         is_random = self.query_strategy == "random"
         is_bald = self.query_strategy == "bald"
@@ -361,8 +414,11 @@ class QuerySelector:
             for it in pending:
                 it.x.record_stream(main)
             low, full_size = model.forward_lowres(xs)
-            idx, _, _ = acq.score_topk_lowres(low, full_size, excl_dev, self.query_strategy, self._k_launch(h, w), crop=(h, w),
-                                              align_corners=lowres_align)
+            if self._region_on:
+                idx = self._region_topk(low, full_size, excl_dev, h, w, lowres_align)
+            else:
+                idx, _, _ = acq.score_topk_lowres(low, full_size, excl_dev, self.query_strategy, self._k_launch(h, w), crop=(h, w),
+                                                  align_corners=lowres_align)
             idx = self._spread(idx, excl_dev, h, w)            # min_pixel_distance: [n,M] -> [n,n_pixels_by_us], on the device
             n, k = idx.shape
             idx_host = torch.empty((n, k), dtype=torch.int32, pin_memory=True)
@@ -386,6 +442,14 @@ class QuerySelector:
                 return
             if pipelined and len({it.size for it in pending}) == 1:
                 launch_pipelined()
+                return
+            if self._region_on and len({it.size for it in pending}) > 1:
+                # equal padded shapes, different crops: one fused batch per size (the per-image routes below are not region-scored)
+                items = list(pending)
+                pending.clear()
+                for size in dict.fromkeys(it.size for it in items):
+                    pending.extend(it for it in items if it.size == size)
+                    flush()
                 return
             if inflight:
                 finish(inflight.pop())
@@ -417,8 +481,11 @@ class QuerySelector:
                     idx_h = self._random_topk(np.stack([it.draws["rmap"] for it in pending]), excl, self._k_launch(h, w))
                 elif fused:
                     excl_t = self._excl_arg(excl)
-                    idx, _, _ = acq.score_topk_lowres(low, full_size, excl_t, self.query_strategy,
-                                                      self._k_launch(h, w), crop=(h, w), align_corners=lowres_align)
+                    if self._region_on:
+                        idx = self._region_topk(low, full_size, excl_t, h, w, lowres_align)
+                    else:
+                        idx, _, _ = acq.score_topk_lowres(low, full_size, excl_t, self.query_strategy,
+                                                          self._k_launch(h, w), crop=(h, w), align_corners=lowres_align)
                     idx_h = self._spread(idx, excl_t, h, w).cpu().numpy().astype(np.int64)
                 else:
                     excl_t = self._excl_arg(excl)

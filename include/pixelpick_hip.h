@@ -294,6 +294,33 @@ int pp_acq_region_table(int64_t r, uint32_t* host_tab);
 int pp_acq_region_score_map(const uint8_t* pred, const float* unc, int64_t B, int64_t C, int64_t H, int64_t W, int64_t r, int mode,
                             int flip, const uint32_t* tab, const uint8_t* exclude, float* out_map, pp_stream_t stream);
 
+/* Class-balanced picks: the picks of one image handed out round-robin over the PREDICTED classes of a rank-ordered pool.  Stands beside
+ * query.py:63-64 - the reference draws n_pixels_by_us of the best top_n_percent at random, blind to classes - as a deterministic
+ * alternative; the reference has no such step, the semantics below are this library's specification (tests/balance_oracle.py restates
+ * them).  Per image b:
+ *   cand     i32 [B,M]: flat pixel indices in RANK order - what every *_topk entry writes to out_idx with k = M
+ *   label    u8 [B,N]: the label map pp_predict_lowres writes;  exclude u8 [B,N] or NULL;  N the pixels per image, 1 <= k <= M <= N
+ *   eligible list position i is eligible iff 0 <= cand[i] < N and (exclude == NULL or exclude[b*N + cand[i]] == 0).  For an ineligible
+ *            position neither label nor exclude is read at an out-of-range index.
+ *   class    c_i = label[b*N + cand[i]], the byte as it stands, 0 .. 255 (unsigned).  There is no class-count argument: always 256 bins,
+ *            no input indexes out of range.
+ *   rank     r_i = #{j < i : j eligible and c_j == c_i}, counted in list order (32-bit counts: a class may hold more than 65 535
+ *            entries of a long list).
+ *   balanced phase  E = the number of eligible positions, n = min(k, E).  The picks are the n eligible positions smallest in the
+ *            lexicographic key (r_i, i), written in that order: round 0 holds the best entry of every class in the pool, in list order,
+ *            round 1 every class's second entry, and so on.  Every class's picks are a prefix of its own ranking; the pick counts of
+ *            two classes differ by at most one unless the smaller class is exhausted.
+ *   fill phase      n < k: the remaining k - n slots take the earliest INELIGIBLE list positions, in list order - k picks always come
+ *            back, as from plain top-k and from pp_spread_select.
+ * A repeated index in cand is two list entries: nothing is de-duplicated.
+ *   out_idx  i32 [B,k] = cand at the picked positions;  out_pos i32 [B,k] their list positions;  out_n i32 [B] = n.
+ * One launch, no workspace, no global atomics (the same bits on every run), no synchronisation.  PP_ERR_BAD_ARG: null cand / label /
+ * out_idx / out_pos / out_n, B / M / N / k < 1, k > M, M > N, N > 2^31 - 1.  PP_ERR_UNSUPPORTED: k > 1024 (pp_spread_select's cap: one
+ * slot counter per round lives in LDS), B > 2^31 - 1.  Every refusal comes before anything is enqueued and no pointer is read. */
+int pp_class_balance_select(const int32_t* cand, int64_t B, int64_t M, int64_t N, int64_t k,
+                            const uint8_t* label, const uint8_t* exclude,
+                            int32_t* out_idx, int32_t* out_pos, int32_t* out_n, pp_stream_t stream);
+
 
 /* =============================================================================================
  * Network layers (DeepLabv3+-MobileNetV2 / FPN-ResNet50 forward + backward), NHWC fp32.

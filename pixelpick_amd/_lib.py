@@ -55,6 +55,7 @@ SIGNATURES = {
     "pp_acq_region_table_words": (_sz, [_i64]),
     "pp_acq_region_table": (_int, [_i64, _p]),
     "pp_acq_region_score_map": (_int, [_p, _p] + [_i64] * 5 + [_int, _int, _p, _p, _p, _p]),
+    "pp_class_balance_select": (_int, [_p] + [_i64] * 4 + [_p, _p, _p, _p, _p, _p]),
     "pp_conv2d_fwd_workspace_bytes": (_sz, [_int] * 10),
     "pp_conv2d_bwd_data_workspace_bytes": (_sz, [_int] * 10),
     "pp_conv2d_fwd": (_int, [_p, _i64, _int, _int, _int, _int, _p, _p, _int, _int, _int, _int, _int, _p, _i64, _int, _p, _sz, _p]),

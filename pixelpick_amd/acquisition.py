@@ -572,3 +572,56 @@ def region_score_map(pred: Optional[torch.Tensor], unc: Optional[torch.Tensor], 
                                                 ex.data_ptr() if ex is not None else None, omap.data_ptr(), _lib.current_stream_ptr(dev))
     _lib.check(rc, "pp_acq_region_score_map")
     return omap
+
+
+# ---- class-balanced picks: round-robin over the predicted classes of a rank-ordered pool (include/pixelpick_hip.h, pp_class_balance_select) ----
+BALANCE_MAX_PICKS = 1024       # one slot counter per round lives in LDS (pp_spread_select's cap): more per image is PP_ERR_UNSUPPORTED
+
+
+def class_balance_select(cand: torch.Tensor, label: torch.Tensor, k: int, exclude=None
+                         ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Round-robin selection over the predicted classes (pp_class_balance_select): cand int32 [B,M] on the GPU, flat pixel indices in
+    RANK order (the idx of any *_topk function called with k = M); label uint8 [B, ...] with N entries per image on the same device
+    (predict_lowres).  An entry is eligible when it lies in [0, N) and is not excluded; its rank inside its class counts the eligible
+    entries of that class in front of it.  The picks are the min(k, eligible) entries smallest in (rank inside the class, list
+    position): the best entry of every class in the pool first, then every class's second entry, and so on; a pool with fewer than
+    k eligible entries is topped up with its earliest ineligible ones.  exclude: [B, ...] with the same N entries per image, or None.
+    Returns (idx int32 [B,k], pos int32 [B,k] = list position of each pick, n int32 [B] = picks of the balanced phase)."""
+    if not isinstance(cand, torch.Tensor) or cand.ndim != 2 or cand.dtype != torch.int32:
+        raise ValueError("cand must be a 2-d int32 tensor [B,M]")
+    if not cand.is_cuda:
+        raise _lib.PixelPickHipError("cand must live on the GPU: the HIP path has no CPU fallback")
+    if not isinstance(label, torch.Tensor) or label.ndim < 2 or label.dtype != torch.uint8:
+        raise ValueError("label must be a uint8 tensor [B, ...] (the label map predict_lowres writes)")
+    if not label.is_cuda or label.device != cand.device:
+        raise _lib.PixelPickHipError("label must live on the GPU with cand: the HIP path has no CPU fallback")
+    cand = cand.contiguous()
+    B, M = cand.shape
+    dev = cand.device
+    if label.shape[0] != B:
+        raise ValueError(f"label holds {label.shape[0]} images, cand {B}")
+    label = label.reshape(B, -1).contiguous()
+    N = label.shape[1]
+    ex = None
+    if exclude is not None:
+        if isinstance(exclude, np.ndarray):
+            exclude = np.ascontiguousarray(exclude)
+        ex = torch.as_tensor(exclude)
+        if ex.ndim < 2 or ex.shape[0] != B:
+            raise ValueError(f"exclude must be [B, ...] with B = {B}, got {tuple(ex.shape)}")
+        if ex.dtype == torch.bool:
+            ex = ex.contiguous().view(torch.uint8)
+        elif ex.dtype != torch.uint8:
+            ex = (ex != 0).contiguous().view(torch.uint8)
+        ex = ex.to(dev, non_blocking=True).reshape(B, -1).contiguous()
+        if ex.shape[1] != N:
+            raise ValueError(f"exclude holds {ex.shape[1]} pixels per image, label {N}")
+    k = int(k)
+    idx = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+    pos = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+    n = torch.empty((B,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().pp_class_balance_select(cand.data_ptr(), B, M, N, k, label.data_ptr(), ex.data_ptr() if ex is not None else None,
+                                                idx.data_ptr(), pos.data_ptr(), n.data_ptr(), _lib.current_stream_ptr(dev))
+    _lib.check(rc, "pp_class_balance_select")
+    return idx, pos, n

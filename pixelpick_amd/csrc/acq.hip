@@ -3409,6 +3409,182 @@ __global__ __launch_bounds__(kRegionMaxWaves * kWave) void region_score_kernel(R
     }
 }
 
+// ---- pp_class_balance_select: round-robin over the predicted classes of a rank-ordered pool (include/pixelpick_hip.h) ---
+// One wave per image, spread_select_kernel's frame.  A pick's output slot is known without a sort: round r opens at slot
+// S(r) = sum_c min(t_c, r) (t_c = the class totals), and inside a round the entries stand in list order - the order the list is
+// walked in.  So:
+//   walk 1   the class totals t_c in LDS (ds_add: integer sums, the same whatever order the lanes arrive in) and E; sixteen chunks of 64
+//            candidates and their gathered bytes in flight (the walk is bound by the latency of the gather, the order does not matter here);
+//   scans    D[v] = #{c : min(t_c, k) == v}, P = prefix(D), Q = prefix(P): S(r) = r T - Q[r-1] with T = P[k] the classes in the pool
+//            (H[q] = T - P[q] classes reach round q).  s_next[r] = S(r), r = 0 .. k; R = the first r with S(r) >= n: rounds >= R hold no pick;
+//   walk 2   in list order, 64 at a time: the rank inside the class from a ballot loop over the chunk's distinct classes (256 running
+//            counters in LDS), then the slot s_next[r]++ from a ballot loop over the chunk's distinct rounds < R; an entry whose slot is
+//            < n is written straight to the output.  Leaves as soon as n picks are out;
+//   fill     only when E < k: a third walk hands the earliest ineligible positions the remaining slots.
+constexpr int kBalanceUnroll = 16;
+
+struct BalanceParams {
+    const int32_t* cand;      // [B,M]
+    const uint8_t* label;     // [B,N]
+    const uint8_t* exclude;   // [B,N] or null
+    int32_t* out_idx;         // [B,k]
+    int32_t* out_pos;         // [B,k]
+    int32_t* out_n;           // [B]
+    int64_t M, N;
+    int k;
+};
+
+// in-place inclusive prefix sum of a[0 .. L) by one wave: a run of consecutive entries per lane, the run totals scanned across lanes
+__device__ __forceinline__ void balance_scan(uint32_t* a, int L, int lane)
+{
+    const int seg = (L + kWave - 1) / kWave;
+    const int lo = min(lane * seg, L), hi = min(lo + seg, L);
+    uint32_t s = 0;
+    for (int i = lo; i < hi; ++i) s += a[i];
+    uint32_t incl = s;
+    for (int off = 1; off < kWave; off <<= 1) {
+        const uint32_t v = __shfl_up(incl, off, kWave);
+        if (lane >= off) incl += v;
+    }
+    uint32_t run = incl - s;
+    for (int i = lo; i < hi; ++i) {
+        run += a[i];
+        a[i] = run;
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(kWave) void class_balance_kernel(BalanceParams p)
+{
+    __shared__ uint32_t s_cnt[256];                  // walk 1: class totals; walk 2: running class counts
+    __shared__ uint32_t s_q[kSpreadMaxK + 1];        // D -> P -> Q
+    __shared__ uint32_t s_next[kSpreadMaxK + 1];     // the next free output slot of round r
+    const int lane = threadIdx.x;
+    const int64_t img = blockIdx.x;
+    const int32_t* cand = p.cand + img * p.M;
+    const uint8_t* label = p.label + img * p.N;
+    const uint8_t* excl = p.exclude ? p.exclude + img * p.N : nullptr;
+    int32_t* out_idx = p.out_idx + img * p.k;
+    int32_t* out_pos = p.out_pos + img * p.k;
+    const int64_t M = p.M;
+    const int k = p.k;
+    const uint64_t below = (1ull << lane) - 1ull;
+    auto load_c = [&](int64_t base) -> int { return base + lane < M ? cand[base + lane] : -1; };
+    // the class of an eligible candidate, -1 for an ineligible one (outside [0, N): neither byte is read; beyond the list: c = -1)
+    auto load_cls = [&](int c) -> int {
+        if (c < 0 || (int64_t)c >= p.N) return -1;
+        const int e = excl ? (int)excl[c] : 0;
+        const int l = (int)label[c];
+        return e == 0 ? l : -1;
+    };
+
+    for (int i = lane; i < 256; i += kWave) s_cnt[i] = 0u;
+    for (int i = lane; i <= k; i += kWave) s_q[i] = 0u;
+    __syncthreads();
+
+    // walk 1: class totals and E
+    int64_t E = 0;
+    {
+        int c[kBalanceUnroll];
+#pragma unroll
+        for (int u = 0; u < kBalanceUnroll; ++u) c[u] = load_c((int64_t)u * kWave);
+        for (int64_t base = 0; base < M; base += kBalanceUnroll * kWave) {
+            int nx[kBalanceUnroll], cl[kBalanceUnroll];
+#pragma unroll
+            for (int u = 0; u < kBalanceUnroll; ++u) nx[u] = load_c(base + (int64_t)(kBalanceUnroll + u) * kWave);
+#pragma unroll
+            for (int u = 0; u < kBalanceUnroll; ++u) cl[u] = load_cls(c[u]);
+#pragma unroll
+            for (int u = 0; u < kBalanceUnroll; ++u) {
+                if (cl[u] >= 0) atomicAdd(&s_cnt[cl[u]], 1u);
+                E += __popcll(__ballot(cl[u] >= 0));
+                c[u] = nx[u];
+            }
+        }
+    }
+    __syncthreads();
+    const int n = (int)(E < (int64_t)k ? E : (int64_t)k);
+    if (lane == 0) p.out_n[img] = n;
+
+    // scans: s_next[r] = S(r) = sum_c min(t_c, r), r = 0 .. k
+    for (int c = lane; c < 256; c += kWave) {
+        const uint32_t t = s_cnt[c];
+        if (t != 0u) atomicAdd(&s_q[t < (uint32_t)k ? t : (uint32_t)k], 1u);
+    }
+    __syncthreads();
+    for (int i = lane; i < 256; i += kWave) s_cnt[i] = 0u;      // from here on: the running counts of walk 2
+    balance_scan(s_q, k + 1, lane);                  // P
+    const uint32_t T = s_q[k];
+    __syncthreads();
+    balance_scan(s_q, k + 1, lane);                  // Q
+    int R = k;
+    for (int r = lane; r <= k; r += kWave) {
+        const uint32_t S = r == 0 ? 0u : (uint32_t)r * T - s_q[r - 1];
+        s_next[r] = S;
+        if (S >= (uint32_t)n && r < R) R = r;
+    }
+    for (int off = kWave / 2; off > 0; off >>= 1) R = min(R, __shfl_xor(R, off, kWave));
+    __syncthreads();
+
+    // walk 2: ranks, slots, picks
+    int taken = 0;
+    {
+        int c0 = load_c(0), c1 = load_c(kWave);
+        int cl0 = load_cls(c0);
+        for (int64_t base = 0; base < M && taken < n; base += kWave) {
+            const int c2 = load_c(base + 2 * kWave);
+            const int cl1 = load_cls(c1);
+            const bool el = cl0 >= 0;
+            int r = 0;
+            uint64_t todo = __ballot(el);
+            while (todo != 0ull) {                   // one turn per distinct class of the chunk
+                const int lc = __shfl(cl0, __ffsll((long long)todo) - 1, kWave);
+                const bool mine = el && cl0 == lc;
+                const uint64_t m = __ballot(mine);
+                const uint32_t seen = s_cnt[lc];     // one word for all lanes: a broadcast
+                if (mine) r = (int)(seen + (uint32_t)__popcll(m & below));
+                if (lane == 0) s_cnt[lc] = seen + (uint32_t)__popcll(m);
+                todo &= ~m;
+            }
+            const bool act = el && r < R;
+            int slot = n;
+            todo = __ballot(act);
+            while (todo != 0ull) {                   // one turn per distinct round of the chunk
+                const int lr = __shfl(r, __ffsll((long long)todo) - 1, kWave);
+                const bool mine = act && r == lr;
+                const uint64_t m = __ballot(mine);
+                const uint32_t first = s_next[lr];
+                if (mine) slot = (int)(first + (uint32_t)__popcll(m & below));
+                if (lane == 0) s_next[lr] = first + (uint32_t)__popcll(m);
+                todo &= ~m;
+            }
+            const bool pick = act && slot < n;       // the last round may be cut short
+            if (pick) {
+                out_idx[slot] = c0;
+                out_pos[slot] = (int)(base + lane);
+            }
+            taken += __popcll(__ballot(pick));
+            __syncthreads();                         // one wave: orders the LDS writes above before the next chunk's reads
+            c0 = c1; cl0 = cl1; c1 = c2;
+        }
+    }
+    if (n == k) return;
+    // fill phase: the earliest ineligible list positions, in list order
+    int filled = n;
+    for (int64_t base = 0; base < M && filled < k; base += kWave) {
+        const int64_t i = base + lane;
+        const int c = load_c(base);
+        const bool take = i < M && load_cls(c) < 0;
+        const uint64_t m = __ballot(take);
+        const int slot = filled + __popcll(m & below);
+        if (take && slot < k) {
+            out_idx[slot] = c;
+            out_pos[slot] = (int)i;
+        }
+        filled += __popcll(m);
+    }
+}
+
 }  // namespace pp
 
 using namespace pp;
@@ -3810,6 +3986,25 @@ int pp_acq_region_score_map(const uint8_t* pred, const float* unc, int64_t B, in
     RegionParams p{pred, unc, tab, exclude, out_map, (int)H, (int)W, (int)C, (int)r, mode, flip ? 1 : 0, (int)tiles_x, (int)tiles_y, waves};
     hipLaunchKernelGGL(region_score_kernel, dim3((unsigned)(B * tiles_x * tiles_y)), dim3(waves * kWave), lds_bytes, as_stream(stream), p);
     return check_launch("region_score_kernel");
+}
+
+int pp_class_balance_select(const int32_t* cand, int64_t B, int64_t M, int64_t N, int64_t k, const uint8_t* label, const uint8_t* exclude,
+                            int32_t* out_idx, int32_t* out_pos, int32_t* out_n, pp_stream_t stream)
+{
+    if (!cand) return fail(PP_ERR_BAD_ARG, "class_balance_select: cand is null");
+    if (!label) return fail(PP_ERR_BAD_ARG, "class_balance_select: label is null");
+    if (!out_idx) return fail(PP_ERR_BAD_ARG, "class_balance_select: out_idx is null");
+    if (!out_pos) return fail(PP_ERR_BAD_ARG, "class_balance_select: out_pos is null");
+    if (!out_n) return fail(PP_ERR_BAD_ARG, "class_balance_select: out_n is null");
+    if (B < 1) return fail(PP_ERR_BAD_ARG, "class_balance_select: B=%lld < 1", (long long)B);
+    if (N < 1 || N > 0x7FFFFFFFll) return fail(PP_ERR_BAD_ARG, "class_balance_select: N=%lld outside [1, 2^31 - 1]", (long long)N);
+    if (M < 1 || M > N) return fail(PP_ERR_BAD_ARG, "class_balance_select: M=%lld outside [1, N=%lld]", (long long)M, (long long)N);
+    if (k < 1 || k > M) return fail(PP_ERR_BAD_ARG, "class_balance_select: k=%lld outside [1, M=%lld]", (long long)k, (long long)M);
+    if (k > kSpreadMaxK) return fail(PP_ERR_UNSUPPORTED, "class_balance_select: k=%lld > %d picks per image", (long long)k, kSpreadMaxK);
+    if (B > 0x7FFFFFFFll) return fail(PP_ERR_UNSUPPORTED, "class_balance_select: B=%lld > 2^31 - 1 images per call", (long long)B);
+    BalanceParams p{cand, label, exclude, out_idx, out_pos, out_n, M, N, (int)k};
+    hipLaunchKernelGGL(class_balance_kernel, dim3((unsigned)B), dim3(kWave), 0, as_stream(stream), p);
+    return check_launch("class_balance_kernel");
 }
 
 int pp_topk_select(const float* scores, int64_t B, int64_t N, int64_t k, int largest, int32_t* out_idx,

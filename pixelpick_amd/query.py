@@ -43,6 +43,16 @@ reference (`model.py:44,83`, `train.py:9,82`, `datasets/*.py` codecs) runs uncha
     on its ranking as on any other.  Out of scope and REFUSED with a ValueError, never a silent fall-back: the MC-dropout routes
     (`use_mc_dropout`, "bald"), the `random` strategy, heads wider than 256 classes and the full-size route (a model without
     `forward_lowres`, FUSED_LOWRES switched off);
+  * `args.class_balanced` (absent, None and False: off, every path as before, the host RNG streams included) replaces the random
+    sub-sample of the best `top_n_percent` (query.py:63-64), which is blind to classes, by a deterministic rule: the pool stays the
+    reference's - M = int(h*w*top_n_percent) rank-ordered candidates per image - and pp_class_balance_select (include/pixelpick_hip.h)
+    hands the n_pixels_by_us picks out round-robin over the PREDICTED classes in it: the best entry of every class first, then every
+    class's second entry, and so on.  The pipelined batch and the fused batch run pp_predict_lowres (the label map; with
+    `region_radius` the one the region score already made) and the selection on the device, nothing new is read back and no
+    position is drawn from numpy's stream.  It works on the region ranking as on any other.  REFUSED with a ValueError, never a
+    silent fall-back: `top_n_percent <= 0` (no pool), `reverse_order`, the `random` and "bald" strategies, `use_mc_dropout`,
+    `min_pixel_distance >= 2`, more than 1024 picks per image, heads wider than 256 classes, the full-size route (a model without
+    `forward_lowres`, FUSED_LOWRES switched off) and an image whose pool is smaller than `n_pixels_by_us`;
   * there is no CPU fallback: tensors must live on the GPU and the extension must be built.
 """
 import os
@@ -101,6 +111,10 @@ class QuerySelector:
         # not in the reference: score a pixel by its (2r+1)^2 window (pp_acq_region_score_map); 0 = off
         self.region_radius = int(getattr(args, "region_radius", 0) or 0)
         self.region_mode = getattr(args, "region_mode", None) or "product"
+        # not in the reference: the picks of an image round-robin over the predicted classes of its top_n_percent pool
+        # (pp_class_balance_select) instead of the random sub-sample; absent / None / False = off
+        self.class_balanced = bool(getattr(args, "class_balanced", False) or False)
+        self._check_balance()
         self._check_bald()
         self._check_spread()
         self._check_region()
@@ -162,9 +176,10 @@ class QuerySelector:
     def _region_on(self) -> bool:
         return self.region_radius >= 1
 
-    def _region_topk(self, low, full_size, excl_dev, h: int, w: int, align: bool) -> torch.Tensor:
+    def _region_topk(self, low, full_size, excl_dev, h: int, w: int, align: bool) -> Tuple[torch.Tensor, torch.Tensor]:
         """The region-scored replacement of one score_topk_lowres launch: label map + score map of the configured strategy (no mask) ->
-        window impurity x window uncertainty with the mask applied -> top-k, the largest first.  int32 [n,_k_launch] on the device."""
+        window impurity x window uncertainty with the mask applied -> top-k, the largest first.  -> (int32 [n,_k_launch], the label
+        map uint8 [n,h,w] it was scored from - class_balanced reads the same one), both on the device."""
         C = int(low.shape[-1])
         if C > 256:
             raise ValueError(f"region_radius = {self.region_radius} needs a label map of bytes: the model has {C} classes")
@@ -172,13 +187,62 @@ class QuerySelector:
         _, _, unc = acq.score_topk_lowres(low, full_size, None, self.query_strategy, 0, crop=(h, w), align_corners=align)
         rmap = acq.region_score_map(pred, unc, self.region_radius, C, exclude=excl_dev, mode=self.region_mode,
                                     flip=not acq.LARGEST[self.query_strategy])
-        return acq.topk_select(rmap.reshape(rmap.shape[0], h * w), self._k_launch(h, w), True)[0]
+        return acq.topk_select(rmap.reshape(rmap.shape[0], h * w), self._k_launch(h, w), True)[0], pred
+
+    def _check_balance(self, model=None):
+        """`class_balanced` replaces the random sub-sample of the best `top_n_percent` by the round-robin over the predicted classes of
+        that pool; whatever has no such pool, no ranking or no single-pass label map is refused by name, never served by another
+        rule.  With a model (at the round): it must expose forward_lowres."""
+        if not self.class_balanced:
+            return
+        k = self.n_pixels_by_us
+        if not self.top_n_percent > 0.:
+            raise ValueError(f"class_balanced cannot be combined with top_n_percent = {self.top_n_percent}: there is no pool to balance - "
+                             f"with the n_pixels_by_us best pixels as the pool the rule returns plain top-k")
+        if self.reverse_order:
+            raise ValueError("class_balanced cannot be combined with reverse_order: its candidate set is a random draw, not a ranked pool")
+        if self.query_strategy in ("random", "bald"):
+            raise ValueError(f"class_balanced cannot be combined with query_strategy = {self.query_strategy!r}: the pool is the ranking of "
+                             f"a single-pass score (entropy, least_confidence, margin_sampling)")
+        if self.use_mc_dropout:
+            raise ValueError("class_balanced cannot be combined with use_mc_dropout: the label of a committee of passes is not specified")
+        if self.min_pixel_distance >= 2:
+            raise ValueError(f"class_balanced cannot be combined with min_pixel_distance = {self.min_pixel_distance}: two selection rules "
+                             f"for one list of candidates")
+        if k > acq.BALANCE_MAX_PICKS:
+            raise ValueError(f"class_balanced selects at most {acq.BALANCE_MAX_PICKS} pixels per image: n_pixels_by_us = {k}")
+        if self.n_classes > 256:
+            raise ValueError(f"class_balanced needs a label map of bytes: n_classes = {self.n_classes} > 256")
+        if model is not None and not (FUSED_LOWRES and hasattr(model, "forward_lowres")):
+            raise ValueError("class_balanced takes the label map from the classifier output: the model needs forward_lowres (and "
+                             "FUSED_LOWRES on); the full-size route is not class-balanced")
+
+    @property
+    def _balance_on(self) -> bool:
+        return bool(self.class_balanced)
+
+    def _balance(self, idx: torch.Tensor, pred, low, full_size, excl_dev, h: int, w: int, align: bool) -> torch.Tensor:
+        """idx int32 [n,M] on the device, the rank-ordered pool of a *_topk launch at k = _k_launch -> the picks of the round
+        [n,n_pixels_by_us]: unchanged without class_balanced, else pp_class_balance_select's on the label map `pred` (made here by
+        pp_predict_lowres unless the region score already made it) - still on the device, nothing read back in between."""
+        if not self._balance_on:
+            return idx
+        k, M = self.n_pixels_by_us, int(idx.shape[1])
+        if M < k:
+            raise ValueError(f"class_balanced: the pool of a {h} x {w} image holds int(h*w*top_n_percent) = {M} candidates, fewer than "
+                             f"n_pixels_by_us = {k}")
+        if pred is None:
+            C = int(low.shape[-1])
+            if C > 256:
+                raise ValueError(f"class_balanced needs a label map of bytes: the model has {C} classes")
+            pred, _ = predict_lowres(low, full_size, crop=(h, w), align_corners=align, want_pred=True)
+        return acq.class_balance_select(idx, pred, k, exclude=excl_dev)[0]
 
     def _excl_arg(self, excl: np.ndarray):
-        """The exclusion mask as a scoring call takes it.  With min_pixel_distance it is uploaded ONCE here: the scorer and
-        pp_spread_select read the same device bytes."""
+        """The exclusion mask as a scoring call takes it.  With min_pixel_distance, region_radius or class_balanced it is uploaded ONCE
+        here: the scorer and the selection read the same device bytes."""
         t = torch.from_numpy(np.ascontiguousarray(excl))
-        return t.view(torch.uint8).to(self.device, non_blocking=True) if self._spread_on or self._region_on else t
+        return t.view(torch.uint8).to(self.device, non_blocking=True) if self._spread_on or self._region_on or self._balance_on else t
 
     def _spread(self, idx: torch.Tensor, excl_dev, h: int, w: int) -> torch.Tensor:
         """idx int32 [n,M] on the device, rank-ordered (a *_topk launch at k = _k_launch) -> the picks of the round [n,n_pixels_by_us]:
@@ -311,7 +375,7 @@ class QuerySelector:
             d["rmap"] = rmap / np.float32(n_draws) if n_draws > 1 else rmap
         if self.reverse_order:
             d["cand"] = self._reverse_order_sampling_mask(h, w).reshape(h, w)                 # query.py:40
-        elif self.top_n_percent > 0.:
+        elif self.top_n_percent > 0. and not self._balance_on:         # class_balanced: the kernel chooses, nothing is drawn
             # query.py:63-64 `np.random.choice(ind, n_pixels_by_us, False)`: numpy draws permutation(len)[:n] and indexes the
             # array with it, so drawing the POSITIONS consumes the same random numbers and picks the same pixels
             # (tests/test_host_logic.py) - and tells which of the read-back entropies belong to them
@@ -336,6 +400,7 @@ class QuerySelector:
         if self.use_mc_dropout:
             model.turn_on_dropout()
 
+        self._check_balance(model)
         self._check_bald()
         self._check_spread()
         self._check_region(model)
@@ -414,12 +479,14 @@ class QuerySelector:
             for it in pending:
                 it.x.record_stream(main)
             low, full_size = model.forward_lowres(xs)
+            pred = None
             if self._region_on:
-                idx = self._region_topk(low, full_size, excl_dev, h, w, lowres_align)
+                idx, pred = self._region_topk(low, full_size, excl_dev, h, w, lowres_align)
             else:
                 idx, _, _ = acq.score_topk_lowres(low, full_size, excl_dev, self.query_strategy, self._k_launch(h, w), crop=(h, w),
                                                   align_corners=lowres_align)
             idx = self._spread(idx, excl_dev, h, w)            # min_pixel_distance: [n,M] -> [n,n_pixels_by_us], on the device
+            idx = self._balance(idx, pred, low, full_size, excl_dev, h, w, lowres_align)      # class_balanced: likewise
             n, k = idx.shape
             idx_host = torch.empty((n, k), dtype=torch.int32, pin_memory=True)
             idx_host.copy_(idx, non_blocking=True)
@@ -443,8 +510,9 @@ class QuerySelector:
             if pipelined and len({it.size for it in pending}) == 1:
                 launch_pipelined()
                 return
-            if self._region_on and len({it.size for it in pending}) > 1:
-                # equal padded shapes, different crops: one fused batch per size (the per-image routes below are not region-scored)
+            if (self._region_on or self._balance_on) and len({it.size for it in pending}) > 1:
+                # equal padded shapes, different crops: one fused batch per size (the per-image routes below are neither region-scored
+                # nor class-balanced)
                 items = list(pending)
                 pending.clear()
                 for size in dict.fromkeys(it.size for it in items):
@@ -481,12 +549,14 @@ class QuerySelector:
                     idx_h = self._random_topk(np.stack([it.draws["rmap"] for it in pending]), excl, self._k_launch(h, w))
                 elif fused:
                     excl_t = self._excl_arg(excl)
+                    pred = None
                     if self._region_on:
-                        idx = self._region_topk(low, full_size, excl_t, h, w, lowres_align)
+                        idx, pred = self._region_topk(low, full_size, excl_t, h, w, lowres_align)
                     else:
                         idx, _, _ = acq.score_topk_lowres(low, full_size, excl_t, self.query_strategy,
                                                           self._k_launch(h, w), crop=(h, w), align_corners=lowres_align)
-                    idx_h = self._spread(idx, excl_t, h, w).cpu().numpy().astype(np.int64)
+                    idx = self._balance(self._spread(idx, excl_t, h, w), pred, low, full_size, excl_t, h, w, lowres_align)
+                    idx_h = idx.cpu().numpy().astype(np.int64)
                 else:
                     excl_t = self._excl_arg(excl)
                     idx, _, _ = acq.score_topk(lg, excl_t, self.query_strategy, self._k_launch(h, w))
@@ -608,7 +678,7 @@ class QuerySelector:
         # strategy, reverse-order candidates, top-5 % sub-sample are drawn per image); for images of other ranks that only needs
         # (h, w), which the dataset provides as metadata (`image_sizes` / `image_size(i)`).  A dataset without it, in a mode that
         # draws, falls back to enumerating the whole loader and skipping.
-        needs_rng = is_random or self.reverse_order or self.top_n_percent > 0.
+        needs_rng = is_random or self.reverse_order or (self.top_n_percent > 0. and not self._balance_on)
         sharded, sizes = None, None
         if world > 1 and getattr(self.dataloader, "batch_size", None) == 1:
             sizes = dist_utils.dataset_image_sizes(dataset)

@@ -321,6 +321,54 @@ int pp_class_balance_select(const int32_t* cand, int64_t B, int64_t M, int64_t N
                             const uint8_t* label, const uint8_t* exclude,
                             int32_t* out_idx, int32_t* out_pos, int32_t* out_n, pp_stream_t stream);
 
+/* Feature-diverse picks: k-centre greedy (core-set) selection over the class-probability vectors of a rank-ordered pool.  Stands beside
+ * query.py:63-64 as the fourth deterministic alternative to the random sub-sample; the reference has no such step, the semantics below
+ * are this library's specification (tests/diverse_oracle.py restates them).
+ *
+ * pp_acq_lowres_prob_at_u8: the features.  pp_acq_lowres_score_at's sibling - the same geometry and validation, the class vector of
+ * listed pixel i (image img_idx[i], flat crop index pix_idx[i]) interpolated to the bits pp_bilinear_fwd writes - but what leaves is the
+ * softmax itself, as bytes: row out[i*ldf .. i*ldf + ldf), byte c < C = min(255, (int) rintf(255.0f * p_c)) with p the fp32 softmax in
+ * the default scorer's arithmetic (m = max, e_c = 2^((x_c - m) log2 e), p_c = e_c / sum e), a NaN probability -> 0; bytes C .. ldf-1
+ * are written as 0.  An entry with img_idx[i] outside [0,B) or pix_idx[i] outside [0,Hc*Wc) gets an all-zero row and `low` is not read
+ * for it.  Rows leave as whole dwords.  ldf >= C, ldf % 4 == 0, out 4-byte aligned, else PP_ERR_BAD_ARG; C > 256: PP_ERR_UNSUPPORTED;
+ * n == 0: PP_OK without a launch; null img_idx / pix_idx / out with n > 0: PP_ERR_BAD_ARG.  Heads up to 64 classes keep the class
+ * vector in registers, wider ones stream it in three passes (max, sum, emit) - the same bytes. */
+int pp_acq_lowres_prob_at_u8(const float* low, int64_t ldx, int64_t B, int64_t C, int64_t h, int64_t w,
+                             int64_t H, int64_t W, int align_corners, int64_t Hc, int64_t Wc,
+                             const int32_t* img_idx, const int32_t* pix_idx, int64_t n,
+                             uint8_t* out, int64_t ldf, pp_stream_t stream);
+
+/* pp_diverse_select: the selection.  Per image b:
+ *   cand     i32 [B,M]: flat pixel indices in RANK order - what every *_topk entry writes to out_idx with k = M
+ *   feat     u8 [B,M,ldf]: row i belongs to LIST POSITION i; only its first F bytes have meaning (1 <= F <= 256, ldf >= F,
+ *            ldf % 4 == 0, feat 4-byte aligned).  No byte of a row past F enters the result.
+ *   eligible pp_class_balance_select's rule: 0 <= cand[i] < N and (exclude == NULL or exclude[b*N + cand[i]] == 0); exclude is never
+ *            read at an out-of-range index.
+ *   D(i,j)   sum_{f<F} (feat[i][f] - feat[j][f])^2 in exact integers (at most 256 * 255^2 = 16 646 400: 32-bit accumulation).
+ *   greedy phase  E = the number of eligible positions, n = min(k, E).  Pick 0 is the earliest eligible position (the pool's most
+ *            uncertain pixel); pick t >= 1 the eligible, not yet picked position i with the largest r_i = min over the picks so far of
+ *            D(i, pick), ties to the smallest i.  A picked position is never picked again, even when r_i = 0 for everything left:
+ *            identical features come back in list order.  Ineligible positions are never centres and never picked here.
+ *   fill phase    n < k: the remaining slots take the earliest INELIGIBLE positions in list order (pp_class_balance_select's rule).
+ * A repeated index in cand is two list entries.
+ *   out_idx  i32 [B,k] = cand at the picked positions;  out_pos i32 [B,k] the positions;  out_n i32 [B] = n;
+ *   out_dist i32 [B,k] = r_i at the moment pick t >= 1 was taken (the k-centre radius sequence: non-increasing over t = 1 .. n-1);
+ *            pick 0 and the fill slots hold -1.
+ * Integer arithmetic only and no global atomics: the same bytes on every run.  One launch, one block per image: the RESIDENT form
+ * (M <= pp_diverse_resident_candidates(F); 0 = no such form in this build) stages the rows once as dword planes in LDS with r behind
+ * them and runs the k steps there; the STREAMING form reads rows and r (the workspace, u32 [B,M]) from memory every step and takes
+ * every M <= N.  workspace: at least pp_diverse_workspace_bytes(B, M, F) bytes (>= 4*B*M; 0 for arguments no launch accepts), 4-byte
+ * aligned, required by both forms.
+ * PP_ERR_BAD_ARG: null cand / feat / out_idx / out_pos / out_dist / out_n / workspace, B / M / N / k / F < 1, k > M, M > N,
+ * N > 2^31 - 1, F > 256, ldf < F or not a multiple of 4, a misaligned feat, a workspace too small.  PP_ERR_UNSUPPORTED: k > 1024 (the
+ * cap of the other two selectors), B > 2^31 - 1, B*M > 2^40.  Every refusal comes before anything is enqueued and no pointer is read. */
+size_t pp_diverse_workspace_bytes(int64_t B, int64_t M, int64_t F);
+int64_t pp_diverse_resident_candidates(int64_t F);   /* host arithmetic only */
+int pp_diverse_select(const int32_t* cand, int64_t B, int64_t M, int64_t N, int64_t k,
+                      const uint8_t* feat, int64_t F, int64_t ldf, const uint8_t* exclude,
+                      int32_t* out_idx, int32_t* out_pos, int32_t* out_dist, int32_t* out_n,
+                      void* workspace, size_t ws_bytes, pp_stream_t stream);
+
 
 /* =============================================================================================
  * Network layers (DeepLabv3+-MobileNetV2 / FPN-ResNet50 forward + backward), NHWC fp32.

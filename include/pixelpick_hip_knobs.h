@@ -21,7 +21,8 @@ void pp_debug_set_reduce_mode(int mode);
 void pp_debug_set_exact_formula(int on);
 /* Tuning knob for the C == 19 flat path: occupancy bound (2/3/4 waves per SIMD, 0 = default) and
  * pixels per thread (4/8, 0 = automatic).  occ 8 / 9: synchronous NHWC kernel / generic strided path; occ 10: the streamed scorers
- * (class vector read from memory in passes) at ANY class count - the tests compare them bit for bit with the register kernels. */
+ * (class vector read from memory in passes) at ANY class count - the tests compare them bit for bit with the register kernels;
+ * occ 11: pp_diverse_select's streaming form at any M (A/B against the resident form, tests). */
 void pp_debug_set_acq_tuning(int occ, int ppt);
 /* Dense conv kernel A/B knobs: low 2 bits 0 = 128x128 large tile (default; measured fastest), 2 = 128x64 tiles;
  * bit 2 = linear instead of XCD-aware tile order; bit 3 = conditional (non-vector) loads; bits 4/5 = cap the large

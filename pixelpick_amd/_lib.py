@@ -56,6 +56,10 @@ SIGNATURES = {
     "pp_acq_region_table": (_int, [_i64, _p]),
     "pp_acq_region_score_map": (_int, [_p, _p] + [_i64] * 5 + [_int, _int, _p, _p, _p, _p]),
     "pp_class_balance_select": (_int, [_p] + [_i64] * 4 + [_p, _p, _p, _p, _p, _p]),
+    "pp_acq_lowres_prob_at_u8": (_int, [_p] + [_i64] * 7 + [_int, _i64, _i64, _p, _p, _i64, _p, _i64, _p]),
+    "pp_diverse_workspace_bytes": (_sz, [_i64] * 3),
+    "pp_diverse_resident_candidates": (_i64, [_i64]),
+    "pp_diverse_select": (_int, [_p] + [_i64] * 4 + [_p, _i64, _i64, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "pp_conv2d_fwd_workspace_bytes": (_sz, [_int] * 10),
     "pp_conv2d_bwd_data_workspace_bytes": (_sz, [_int] * 10),
     "pp_conv2d_fwd": (_int, [_p, _i64, _int, _int, _int, _int, _p, _p, _int, _int, _int, _int, _int, _p, _i64, _int, _p, _sz, _p]),
@@ -254,7 +258,7 @@ def lib():
 # arguments) and re-issued from a tight loop.  Unlike a hipGraph the replay keeps the two-queue eager schedule (main stream +
 # weight-gradient stream, the all-reduce under the encoder backward) - profiles/r02_graph_replay.txt shows why the graph loses.
 _NOT_LAUNCHES = ("pp_version", "pp_last_error", "pp_bn_fused_capacity", "pp_bn_fused_rows_cached", "pp_set_comm_cu_reserve",
-                 "pp_get_comm_cu_reserve", "pp_acq_region_table_words", "pp_acq_region_table")
+                 "pp_get_comm_cu_reserve", "pp_acq_region_table_words", "pp_acq_region_table", "pp_diverse_resident_candidates")
 
 
 def _is_launch(name: str) -> bool:

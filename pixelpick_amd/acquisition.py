@@ -625,3 +625,92 @@ def class_balance_select(cand: torch.Tensor, label: torch.Tensor, k: int, exclud
                                                 idx.data_ptr(), pos.data_ptr(), n.data_ptr(), _lib.current_stream_ptr(dev))
     _lib.check(rc, "pp_class_balance_select")
     return idx, pos, n
+
+
+# ---- feature-diverse picks: k-centre greedy over the class probabilities of a rank-ordered pool (include/pixelpick_hip.h, pp_diverse_select) ----
+DIVERSE_MAX_PICKS = 1024       # the cap of the other two selectors (pp_spread_select, pp_class_balance_select): more per image is PP_ERR_UNSUPPORTED
+DIVERSE_MAX_FEATURES = 256     # bytes of a feature row that enter a distance: one per class of the widest label map
+
+
+def prob_at_lowres(low: torch.Tensor, size, img_idx, pix_idx, crop=None, align_corners: bool = True, ldf: Optional[int] = None
+                   ) -> torch.Tensor:
+    """The class probabilities (softmax of the interpolated class vector, the default scorer's arithmetic) at listed pixels, as bytes
+    min(255, rint(255 p)): pixel i = image img_idx[i], flat index pix_idx[i] = y*crop_w + x (pp_acq_lowres_prob_at_u8).  ldf: the row
+    pitch, a multiple of 4 and at least C (None: C rounded up to 4); bytes C .. ldf-1 are 0, and so is the whole row of an entry
+    outside the batch or the crop.  -> uint8 [n, ldf] on the GPU."""
+    B, h, w, C, ldx, H, W, Hc, Wc = _lowres_geom(low, size, crop)
+    dev = low.device
+    ii = torch.as_tensor(img_idx).to(torch.int32).to(dev).contiguous()
+    pp = torch.as_tensor(pix_idx).to(torch.int32).to(dev).contiguous()
+    if ii.shape != pp.shape or ii.ndim != 1:
+        raise ValueError("img_idx and pix_idx must be 1-d and of equal length")
+    ldf = (C + 3) // 4 * 4 if ldf is None else int(ldf)
+    if ldf < C or ldf % 4:
+        raise ValueError(f"ldf = {ldf} must be a multiple of 4 and at least C = {C}")
+    n = ii.numel()
+    out = torch.empty((n, ldf), dtype=torch.uint8, device=dev)
+    if n == 0:
+        return out
+    with torch.cuda.device(dev):
+        rc = _lib.lib().pp_acq_lowres_prob_at_u8(low.data_ptr(), ldx, B, C, h, w, H, W, int(bool(align_corners)), Hc, Wc, ii.data_ptr(),
+                                                 pp.data_ptr(), n, out.data_ptr(), ldf, _lib.current_stream_ptr(dev))
+    _lib.check(rc, "pp_acq_lowres_prob_at_u8")
+    return out
+
+
+def diverse_select(cand: torch.Tensor, feat: torch.Tensor, k: int, n_features: Optional[int] = None, exclude=None,
+                   n_pixels: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """k-centre greedy selection in feature space (pp_diverse_select): cand int32 [B,M] on the GPU, flat pixel indices in RANK order
+    (the idx of any *_topk function called with k = M); feat uint8 [B,M,ldf] on the same device, row i the features of list position
+    i, of which the first n_features bytes count (None: all ldf).  An entry is eligible when it lies in [0, N) and is not excluded.
+    Pick 0 is the earliest eligible entry; every further pick is the eligible entry farthest (sum of squared byte differences) from
+    the picks so far, ties to the earliest; a pool with fewer than k eligible entries is topped up with its earliest ineligible ones.
+    exclude: [B, ...] with N entries per image, or None.  n_pixels: N, the pixels per image; None: that of exclude, and without
+    exclude 2^31 - 1 (every non-negative index is inside).  Returns (idx int32 [B,k], pos int32 [B,k] = list position of each pick, dist int32 [B,k] = squared
+    distance to the nearest earlier pick, -1 for pick 0 and the top-up, n int32 [B] = picks of the greedy phase)."""
+    if not isinstance(cand, torch.Tensor) or cand.ndim != 2 or cand.dtype != torch.int32:
+        raise ValueError("cand must be a 2-d int32 tensor [B,M]")
+    if not cand.is_cuda:
+        raise _lib.PixelPickHipError("cand must live on the GPU: the HIP path has no CPU fallback")
+    if not isinstance(feat, torch.Tensor) or feat.ndim != 3 or feat.dtype != torch.uint8:
+        raise ValueError("feat must be a uint8 tensor [B,M,ldf] (the rows prob_at_lowres writes)")
+    if not feat.is_cuda or feat.device != cand.device:
+        raise _lib.PixelPickHipError("feat must live on the GPU with cand: the HIP path has no CPU fallback")
+    cand = cand.contiguous()
+    B, M = cand.shape
+    dev = cand.device
+    if feat.shape[0] != B:
+        raise ValueError(f"feat holds {feat.shape[0]} images, cand {B}")
+    if feat.shape[1] != M:
+        raise ValueError(f"feat holds {feat.shape[1]} rows per image, cand {M} list entries")
+    feat = feat.contiguous()
+    ldf = feat.shape[2]
+    F = ldf if n_features is None else int(n_features)
+    ex, N = None, 0x7FFFFFFF if n_pixels is None else int(n_pixels)
+    if exclude is not None:
+        if isinstance(exclude, np.ndarray):
+            exclude = np.ascontiguousarray(exclude)
+        ex = torch.as_tensor(exclude)
+        if ex.ndim < 2 or ex.shape[0] != B:
+            raise ValueError(f"exclude must be [B, ...] with B = {B}, got {tuple(ex.shape)}")
+        if ex.dtype == torch.bool:
+            ex = ex.contiguous().view(torch.uint8)
+        elif ex.dtype != torch.uint8:
+            ex = (ex != 0).contiguous().view(torch.uint8)
+        ex = ex.to(dev, non_blocking=True).reshape(B, -1).contiguous()
+        if n_pixels is not None and ex.shape[1] != N:
+            raise ValueError(f"exclude holds {ex.shape[1]} pixels per image, n_pixels = {N}")
+        N = ex.shape[1]
+    k = int(k)
+    L = _lib.lib()
+    idx = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+    pos = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+    dist = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+    n = torch.empty((B,), dtype=torch.int32, device=dev)
+    ws = _ws(L.pp_diverse_workspace_bytes(B, M, F), dev)
+    with torch.cuda.device(dev):
+        rc = L.pp_diverse_select(cand.data_ptr(), B, M, N, k, feat.data_ptr(), F, ldf, ex.data_ptr() if ex is not None else None,
+                                 idx.data_ptr(), pos.data_ptr(), dist.data_ptr(), n.data_ptr(), ws.data_ptr(), ws.numel(),
+                                 _lib.current_stream_ptr(dev))
+    _lib.check(rc, "pp_diverse_select")
+    return idx, pos, dist, n

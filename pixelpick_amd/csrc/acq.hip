@@ -3585,6 +3585,262 @@ __global__ __launch_bounds__(kWave) void class_balance_kernel(BalanceParams p)
     }
 }
 
+// ---- pp_acq_lowres_prob_at_u8: the class probabilities at listed pixels as bytes (include/pixelpick_hip.h) -------------------
+// pp_acq_lowres_score_at's sibling: one thread per listed pixel, the class vector interpolated with the same taps, the softmax with the
+// scorer's arithmetic (acq_score.h: m = max, e_c = fast_exp(x_c - m), S = sum e_c in class order, p_c = e_c / S).  A row leaves as whole
+// dwords, four codes each; an entry outside the batch or the crop writes a zero row and never reads `low`.
+__device__ __forceinline__ uint32_t prob_code(float e, float S)
+{
+    const float v = 255.0f * (e / S);
+    return v == v ? (uint32_t)min(255, (int)rintf(v)) : 0u;      // NaN -> 0
+}
+
+// true: entry i is in range; otherwise its row was zeroed here
+__device__ __forceinline__ bool prob_at_entry(int img, int pix, int B, int npix, uint32_t* row, int ldw)
+{
+    if (img >= 0 && img < B && pix >= 0 && pix < npix) return true;
+    for (int j = 0; j < ldw; ++j) row[j] = 0u;
+    return false;
+}
+
+template <int CMAX, bool EXACT>
+__global__ __launch_bounds__(kBlock) void prob_at_kernel(const float* low, int64_t ldx, int B, int h, int w, float sh, float sw, int align,
+                                                       int Wc, int npix, int C_, const int32_t* img_idx, const int32_t* pix_idx, int64_t n,
+                                                       uint32_t* out, int ldw)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int C = EXACT ? CMAX : C_;
+    const int img = img_idx[i], pix = pix_idx[i];
+    uint32_t* row = out + i * ldw;
+    if (!prob_at_entry(img, pix, B, npix, row, ldw)) return;
+    const int Y = pix / Wc, X = pix - Y * Wc;
+    const Lerp lh = lerp_src(Y, h, sh, align), lw = lerp_src(X, w, sw, align);
+    const float* base = low + (int64_t)img * h * w * ldx;
+    float x[CMAX];
+    const auto tp = lowres_taps(base, ldx, w, lh, lw);
+    lowres_class_vector<CMAX, EXACT>(tp, C, x);
+    float m = x[0];
+#pragma unroll
+    for (int c = 1; c < CMAX; ++c)
+        if (EXACT || c < C) m = fmaxf(m, x[c]);
+    float S = 0.0f;
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c)
+        if (EXACT || c < C) {
+            x[c] = fast_exp(x[c] - m);
+            S += x[c];
+        }
+    constexpr int kWords = (CMAX + 3) / 4;
+#pragma unroll
+    for (int j = 0; j < kWords; ++j) {
+        uint32_t word = 0u;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int c = 4 * j + b;
+            if (c < CMAX && (EXACT || c < C)) word |= prob_code(x[c], S) << (8 * b);
+        }
+        if (j < ldw) row[j] = word;
+    }
+    for (int j = kWords; j < ldw; ++j) row[j] = 0u;
+}
+
+// heads wider than the register forms: three passes over the pixel's classes (max, sum, emit), the later ones served by L2; the same
+// expressions in the same order - forced onto a C <= 64 input the bytes are those of prob_at_kernel
+__global__ __launch_bounds__(kBlock) void prob_at_stream_kernel(const float* low, int64_t ldx, int B, int h, int w, float sh, float sw,
+                                                              int align, int Wc, int npix, int C, const int32_t* img_idx,
+                                                              const int32_t* pix_idx, int64_t n, uint32_t* out, int ldw)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int img = img_idx[i], pix = pix_idx[i];
+    uint32_t* row = out + i * ldw;
+    if (!prob_at_entry(img, pix, B, npix, row, ldw)) return;
+    const int Y = pix / Wc, X = pix - Y * Wc;
+    const Lerp lh = lerp_src(Y, h, sh, align), lw = lerp_src(X, w, sw, align);
+    const float* base = low + (int64_t)img * h * w * ldx;
+    const auto tp = lowres_taps(base, ldx, w, lh, lw);
+    float m = tp.at(0);
+    for (int c = 1; c < C; ++c) m = fmaxf(m, tp.at(c));
+    float S = 0.0f;
+    for (int c = 0; c < C; ++c) S += fast_exp(tp.at(c) - m);
+    for (int j = 0; j < ldw; ++j) {
+        uint32_t word = 0u;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int c = 4 * j + b;
+            if (c < C) word |= prob_code(fast_exp(tp.at(c) - m), S) << (8 * b);
+        }
+        row[j] = word;
+    }
+}
+
+// ---- pp_diverse_select: k-centre greedy over the feature rows of a rank-ordered pool (include/pixelpick_hip.h) ------------------
+// One block per image.  r_i = the squared distance of list position i to the nearest pick so far: kDivFar for an eligible position
+// before the first pick (so pick 0 is the earliest eligible one by the tie rule alone), kDivDead for an ineligible or picked one.  A
+// step is one pass over the image's candidates: r_i = min(r_i, D(i, last)), the best (r_i, smallest i) of a lane as the 64-bit key
+// r << 32 | ~i, its maximum over the block by wave shuffles and one LDS round, the winner's row to s_last for the next step.  Eight
+// candidates per thread are in flight against one broadcast read of s_last.  D = |a|^2 + |b|^2 - 2 a.b from packed byte dot products,
+// exact in 32 bits (at most 256 * 255^2).
+//   RES   the rows staged once as dword planes plane[j][i] (consecutive lanes read consecutive dwords: no bank conflict) with r behind
+//         them, all k steps out of LDS;
+//   else  rows and r (the caller's workspace) read from memory every step.
+constexpr int kDivThreads = 1024;
+constexpr int kDivChunk = 8;
+constexpr uint32_t kDivDead = 0xFFFFFFFFu, kDivFar = 0x7FFFFFFFu;
+constexpr size_t kDivLdsMax = 160 * 1024 - 1024;     // the dynamic part: the static arrays below take less than the 1 KiB left
+
+struct DiverseParams {
+    const int32_t* cand;      // [B,M]
+    const uint32_t* feat;     // [B,M,ldw] dwords
+    const uint8_t* exclude;   // [B,N] or null
+    int32_t* out_idx;         // [B,k]
+    int32_t* out_pos;         // [B,k]
+    int32_t* out_dist;        // [B,k]
+    int32_t* out_n;           // [B]
+    uint32_t* r;              // [B,M] (streaming form)
+    int64_t M, N;
+    int ldw, dw;              // dwords per row: pitch, and those that hold features
+    uint32_t tail_mask;       // of dword dw - 1
+    int k;
+};
+
+__device__ __forceinline__ uint32_t dot4_u8(uint32_t a, uint32_t b, uint32_t acc)
+{
+#if __has_builtin(__builtin_amdgcn_udot4)
+    return __builtin_amdgcn_udot4(a, b, acc, false);
+#else
+    return acc + (a & 255u) * (b & 255u) + ((a >> 8) & 255u) * ((b >> 8) & 255u) + ((a >> 16) & 255u) * ((b >> 16) & 255u) + (a >> 24) * (b >> 24);
+#endif
+}
+
+template <bool RES>
+__global__ __launch_bounds__(kDivThreads) void diverse_kernel(DiverseParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_div[];      // RES: plane[dw][M], then r[M]
+    __shared__ uint32_t s_last[64];
+    __shared__ uint32_t s_nb;
+    __shared__ uint64_t s_red[kDivThreads / kWave];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid >> 6;
+    const int64_t img = blockIdx.x;
+    const int64_t M = p.M;
+    const int dw = p.dw, ldw = p.ldw, k = p.k;
+    const int32_t* cand = p.cand + img * M;
+    const uint32_t* feat = p.feat + img * M * ldw;
+    const uint8_t* excl = p.exclude ? p.exclude + img * p.N : nullptr;
+    int32_t* out_idx = p.out_idx + img * k;
+    int32_t* out_pos = p.out_pos + img * k;
+    int32_t* out_dist = p.out_dist + img * k;
+    uint32_t* r = RES ? s_div + (int64_t)dw * M : p.r + img * M;
+    auto eligible = [&](int c) -> bool { return c >= 0 && (int64_t)c < p.N && (!excl || excl[c] == 0); };
+    // dword j of row i, the bytes past F cleared
+    auto word = [&](int64_t i, int j) -> uint32_t {
+        if constexpr (RES) return s_div[(int64_t)j * M + i];
+        else return feat[i * ldw + j] & (j == dw - 1 ? p.tail_mask : 0xFFFFFFFFu);
+    };
+
+    for (int64_t i = tid; i < M; i += kDivThreads) r[i] = eligible(cand[i]) ? kDivFar : kDivDead;
+    if constexpr (RES) {
+        const int64_t words = M * ldw;
+        for (int64_t e = tid; e < words; e += kDivThreads) {
+            const int64_t i = e / ldw;
+            const int j = (int)(e - i * ldw);
+            if (j < dw) s_div[(int64_t)j * M + i] = feat[e] & (j == dw - 1 ? p.tail_mask : 0xFFFFFFFFu);
+        }
+    }
+    __syncthreads();
+
+    int n = 0;
+    int64_t last = -1;
+    for (; n < k; ++n) {
+        uint64_t best = 0ull;
+        const uint32_t nb = n > 0 ? s_nb : 0u;
+        for (int64_t base = tid; base < M; base += (int64_t)kDivThreads * kDivChunk) {
+            uint32_t rv[kDivChunk];
+#pragma unroll
+            for (int u = 0; u < kDivChunk; ++u) {
+                const int64_t i = base + (int64_t)u * kDivThreads;
+                rv[u] = i < M ? r[i] : kDivDead;
+            }
+            if (n > 0) {
+                uint32_t aa[kDivChunk], ab[kDivChunk];
+#pragma unroll
+                for (int u = 0; u < kDivChunk; ++u) { aa[u] = 0u; ab[u] = 0u; }
+                for (int j = 0; j < dw; ++j) {
+                    const uint32_t b = s_last[j];
+#pragma unroll
+                    for (int u = 0; u < kDivChunk; ++u)
+                        if (rv[u] != kDivDead) {
+                            const uint32_t a = word(base + (int64_t)u * kDivThreads, j);
+                            aa[u] = dot4_u8(a, a, aa[u]);
+                            ab[u] = dot4_u8(a, b, ab[u]);
+                        }
+                }
+#pragma unroll
+                for (int u = 0; u < kDivChunk; ++u)
+                    if (rv[u] != kDivDead) {
+                        const int64_t i = base + (int64_t)u * kDivThreads;
+                        rv[u] = i == last ? kDivDead : min(rv[u], nb + aa[u] - 2u * ab[u]);
+                        r[i] = rv[u];
+                    }
+            }
+#pragma unroll
+            for (int u = 0; u < kDivChunk; ++u)
+                if (rv[u] != kDivDead) {
+                    const uint64_t key = ((uint64_t)rv[u] << 32) | (uint32_t)~(uint32_t)(base + (int64_t)u * kDivThreads);
+                    best = key > best ? key : best;
+                }
+        }
+#pragma unroll
+        for (int off = kWave / 2; off > 0; off >>= 1) {
+            const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(best >> 32), off, kWave);
+            const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)best, off, kWave);
+            const uint64_t o = ((uint64_t)hi << 32) | lo;
+            best = o > best ? o : best;
+        }
+        if (lane == 0) s_red[wv] = best;
+        __syncthreads();
+        uint64_t win = 0ull;
+#pragma unroll
+        for (int v = 0; v < kDivThreads / kWave; ++v) win = s_red[v] > win ? s_red[v] : win;
+        if (win == 0ull) break;                      // no eligible position is left (the same word in every thread)
+        last = (int64_t)(~(uint32_t)win);
+        if (tid == 0) {
+            out_idx[n] = cand[last];
+            out_pos[n] = (int)last;
+            out_dist[n] = n == 0 ? -1 : (int)(uint32_t)(win >> 32);
+        }
+        if (tid < kWave) {                           // the winner's row and its squared norm for the next step
+            const uint32_t b = tid < dw ? word(last, tid) : 0u;
+            s_last[tid] = b;
+            uint32_t nrm = dot4_u8(b, b, 0u);
+#pragma unroll
+            for (int off = kWave / 2; off > 0; off >>= 1) nrm += (uint32_t)__shfl_xor((int)nrm, off, kWave);
+            if (tid == 0) s_nb = nrm;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) p.out_n[img] = n;
+    if (n == k || tid >= kWave) return;
+    // fill phase (one wave): the earliest ineligible list positions, in list order.  Fewer than k positions are eligible, so the
+    // walk ends inside the first 2 k positions
+    const uint64_t below = (1ull << lane) - 1ull;
+    int filled = n;
+    for (int64_t base = 0; base < M && filled < k; base += kWave) {
+        const int64_t i = base + lane;
+        const int c = i < M ? cand[i] : 0;
+        const bool take = i < M && !eligible(c);
+        const uint64_t m = __ballot(take);
+        const int slot = filled + __popcll(m & below);
+        if (take && slot < k) {
+            out_idx[slot] = c;
+            out_pos[slot] = (int)i;
+            out_dist[slot] = -1;
+        }
+        filled += __popcll(m);
+    }
+}
+
 }  // namespace pp
 
 using namespace pp;
@@ -3622,7 +3878,7 @@ void pp_debug_set_acq_tuning(int occ, int ppt)
     g_acq_strat_spec = (occ >> 10) & 1 ? 0 : 1;
     g_nt_off = (occ >> 11) & 1;
     occ &= 0xFF;
-    g_tune_occ = (occ == 2 || occ == 3 || occ == 4 || occ == 8 || occ == 9 || occ == 10) ? occ : 0;   // 10: streamed class vector at any C (A/B, tests)
+    g_tune_occ = (occ == 2 || occ == 3 || occ == 4 || occ == 8 || occ == 9 || occ == 10 || occ == 11) ? occ : 0;   // 10: streamed class vector at any C (A/B, tests); 11: pp_diverse_select's streaming form at any M
     g_tune_ppt = (ppt == 4 || ppt == 8) ? ppt : 0;
 }
 #endif
@@ -4005,6 +4261,95 @@ int pp_class_balance_select(const int32_t* cand, int64_t B, int64_t M, int64_t N
     BalanceParams p{cand, label, exclude, out_idx, out_pos, out_n, M, N, (int)k};
     hipLaunchKernelGGL(class_balance_kernel, dim3((unsigned)B), dim3(kWave), 0, as_stream(stream), p);
     return check_launch("class_balance_kernel");
+}
+
+int pp_acq_lowres_prob_at_u8(const float* low, int64_t ldx, int64_t B, int64_t C, int64_t h, int64_t w, int64_t H, int64_t W,
+                             int align_corners, int64_t Hc, int64_t Wc, const int32_t* img_idx, const int32_t* pix_idx, int64_t n,
+                             uint8_t* out, int64_t ldf, pp_stream_t stream)
+{
+    if (int rc = validate_lowres(low, ldx, B, C, h, w, H, W, Hc, Wc, PP_ACQ_ENTROPY)) return rc;
+    if (C > 256) return fail(PP_ERR_UNSUPPORTED, "prob_at_u8: C=%lld > 256 classes", (long long)C);
+    if (B > 0x7FFFFFFFll) return fail(PP_ERR_UNSUPPORTED, "prob_at_u8: B=%lld > 2^31 - 1 images", (long long)B);
+    if (ldf < C || ldf % 4 != 0 || ldf > 0x7FFFFFFFll)
+        return fail(PP_ERR_BAD_ARG, "prob_at_u8: ldf=%lld must be a multiple of 4 and at least C=%lld", (long long)ldf, (long long)C);
+    if (reinterpret_cast<uintptr_t>(out) % 4 != 0) return fail(PP_ERR_BAD_ARG, "prob_at_u8: out is not 4-byte aligned");
+    if (n == 0) return PP_OK;
+    if (n < 0 || !img_idx || !pix_idx || !out) return fail(PP_ERR_BAD_ARG, "prob_at_u8: null pointer or n < 0");
+    if (cdiv(n, kBlock) > 0x7FFFFFFFll) return fail(PP_ERR_UNSUPPORTED, "prob_at_u8: n=%lld listed pixels", (long long)n);
+    float sh, sw;
+    lowres_scales(h, w, H, W, align_corners, sh, sw);
+    hipStream_t st = as_stream(stream);
+    dim3 grid((unsigned)cdiv(n, kBlock)), block(kBlock);
+    const int al = align_corners ? 1 : 0;
+    uint32_t* out32 = reinterpret_cast<uint32_t*>(out);
+    if (stream_classes(C)) {
+        hipLaunchKernelGGL(prob_at_stream_kernel, grid, block, 0, st, low, ldx, (int)B, (int)h, (int)w, sh, sw, al, (int)Wc, (int)(Hc * Wc),
+                           (int)C, img_idx, pix_idx, n, out32, (int)(ldf / 4));
+        return check_launch("prob_at_stream_kernel");
+    }
+    lowres_by_classes(C, [&](auto cmax, auto exact) {
+        hipLaunchKernelGGL((prob_at_kernel<decltype(cmax)::value, decltype(exact)::value>), grid, block, 0, st, low, ldx, (int)B, (int)h, (int)w,
+                           sh, sw, al, (int)Wc, (int)(Hc * Wc), (int)C, img_idx, pix_idx, n, out32, (int)(ldf / 4));
+        return 0;
+    });
+    return check_launch("prob_at_kernel");
+}
+
+// the largest M the resident form of diverse_kernel takes: the planes of M rows and r behind them in the LDS one block may ask for
+int64_t pp_diverse_resident_candidates(int64_t F)
+{
+    if (F < 1 || F > 256) return 0;
+    return (int64_t)(kDivLdsMax / (4 * ((size_t)cdiv(F, 4) + 1)));
+}
+
+size_t pp_diverse_workspace_bytes(int64_t B, int64_t M, int64_t F)
+{
+    if (B < 1 || M < 1 || F < 1 || F > 256 || B > 0x7FFFFFFFll || M > 0x7FFFFFFFll || B * M > (1ll << 40)) return 0;
+    return align_up((size_t)B * M * 4, 256);         // r, u32 [B,M]: read by the streaming form only
+}
+
+int pp_diverse_select(const int32_t* cand, int64_t B, int64_t M, int64_t N, int64_t k, const uint8_t* feat, int64_t F, int64_t ldf,
+                      const uint8_t* exclude, int32_t* out_idx, int32_t* out_pos, int32_t* out_dist, int32_t* out_n, void* workspace,
+                      size_t ws_bytes, pp_stream_t stream)
+{
+    if (!cand) return fail(PP_ERR_BAD_ARG, "diverse_select: cand is null");
+    if (!feat) return fail(PP_ERR_BAD_ARG, "diverse_select: feat is null");
+    if (!out_idx) return fail(PP_ERR_BAD_ARG, "diverse_select: out_idx is null");
+    if (!out_pos) return fail(PP_ERR_BAD_ARG, "diverse_select: out_pos is null");
+    if (!out_dist) return fail(PP_ERR_BAD_ARG, "diverse_select: out_dist is null");
+    if (!out_n) return fail(PP_ERR_BAD_ARG, "diverse_select: out_n is null");
+    if (!workspace) return fail(PP_ERR_BAD_ARG, "diverse_select: workspace is null");
+    if (B < 1) return fail(PP_ERR_BAD_ARG, "diverse_select: B=%lld < 1", (long long)B);
+    if (N < 1 || N > 0x7FFFFFFFll) return fail(PP_ERR_BAD_ARG, "diverse_select: N=%lld outside [1, 2^31 - 1]", (long long)N);
+    if (M < 1 || M > N) return fail(PP_ERR_BAD_ARG, "diverse_select: M=%lld outside [1, N=%lld]", (long long)M, (long long)N);
+    if (k < 1 || k > M) return fail(PP_ERR_BAD_ARG, "diverse_select: k=%lld outside [1, M=%lld]", (long long)k, (long long)M);
+    if (F < 1 || F > 256) return fail(PP_ERR_BAD_ARG, "diverse_select: F=%lld outside [1, 256]", (long long)F);
+    if (ldf < F || ldf % 4 != 0 || ldf > 0x7FFFFFFFll)
+        return fail(PP_ERR_BAD_ARG, "diverse_select: ldf=%lld must be a multiple of 4 and at least F=%lld", (long long)ldf, (long long)F);
+    if (reinterpret_cast<uintptr_t>(feat) % 4 != 0) return fail(PP_ERR_BAD_ARG, "diverse_select: feat is not 4-byte aligned");
+    if (k > kSpreadMaxK) return fail(PP_ERR_UNSUPPORTED, "diverse_select: k=%lld > %d picks per image", (long long)k, kSpreadMaxK);
+    if (B > 0x7FFFFFFFll) return fail(PP_ERR_UNSUPPORTED, "diverse_select: B=%lld > 2^31 - 1 images per call", (long long)B);
+    if (B * M > (1ll << 40)) return fail(PP_ERR_UNSUPPORTED, "diverse_select: B*M=%lld list entries per call", (long long)(B * M));
+    const size_t need = pp_diverse_workspace_bytes(B, M, F);
+    if (ws_bytes < need || reinterpret_cast<uintptr_t>(workspace) % 4 != 0)
+        return fail(PP_ERR_BAD_ARG, "diverse_select: workspace of %zu bytes, %zu needed (4-byte aligned)", ws_bytes, need);
+    const int dw = (int)cdiv(F, 4);
+    const uint32_t tail = F % 4 ? (1u << (8 * (F % 4))) - 1u : 0xFFFFFFFFu;
+    DiverseParams p{cand, reinterpret_cast<const uint32_t*>(feat), exclude, out_idx, out_pos, out_dist, out_n,
+                    reinterpret_cast<uint32_t*>(workspace), M, N, (int)(ldf / 4), dw, tail, (int)k};
+    hipStream_t st = as_stream(stream);
+    if (M <= pp_diverse_resident_candidates(F) && g_tune_occ != 11) {
+        static bool attr_set = false;
+        if (!attr_set) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(diverse_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)kDivLdsMax);
+            attr_set = true;
+        }
+        hipLaunchKernelGGL(diverse_kernel<true>, dim3((unsigned)B), dim3(kDivThreads), (size_t)(dw + 1) * M * 4, st, p);
+        return check_launch("diverse_resident_kernel");
+    }
+    hipLaunchKernelGGL(diverse_kernel<false>, dim3((unsigned)B), dim3(kDivThreads), 0, st, p);
+    return check_launch("diverse_stream_kernel");
 }
 
 int pp_topk_select(const float* scores, int64_t B, int64_t N, int64_t k, int largest, int32_t* out_idx,

@@ -79,6 +79,8 @@ const Entry kEntries[] = {
     PP_PLAN_ENTRY(pp_spread_select),
     PP_PLAN_ENTRY(pp_acq_region_score_map),
     PP_PLAN_ENTRY(pp_class_balance_select),
+    PP_PLAN_ENTRY(pp_acq_lowres_prob_at_u8),
+    PP_PLAN_ENTRY(pp_diverse_select),
     PP_PLAN_ENTRY(pp_conv2d_fwd),
     PP_PLAN_ENTRY(pp_conv2d_fwd_stats),
     PP_PLAN_ENTRY(pp_bn_train_fwd_partials),

@@ -53,6 +53,16 @@ reference (`model.py:44,83`, `train.py:9,82`, `datasets/*.py` codecs) runs uncha
     silent fall-back: `top_n_percent <= 0` (no pool), `reverse_order`, the `random` and "bald" strategies, `use_mc_dropout`,
     `min_pixel_distance >= 2`, more than 1024 picks per image, heads wider than 256 classes, the full-size route (a model without
     `forward_lowres`, FUSED_LOWRES switched off) and an image whose pool is smaller than `n_pixels_by_us`;
+  * `args.diverse_picks` (absent, None and False: off, every path as before, the host RNG streams included) replaces the random
+    sub-sample of the best `top_n_percent` (query.py:63-64) by core-set / k-centre greedy selection in the model's own output space:
+    the pool stays the reference's - M = int(h*w*top_n_percent) rank-ordered candidates per image - pp_acq_lowres_prob_at_u8 writes
+    every candidate's class probabilities as bytes and pp_diverse_select (include/pixelpick_hip.h) takes the pool's most uncertain
+    pixel first, then n_pixels_by_us - 1 times the candidate farthest from the picks so far.  The pipelined batch and the fused batch
+    run both on the device, nothing new is read back and no position is drawn from numpy's stream.  It works on the region ranking
+    as on any other.  REFUSED with a ValueError, never a silent fall-back: `top_n_percent <= 0` (no pool), `reverse_order`, the
+    `random` and "bald" strategies, `use_mc_dropout`, `min_pixel_distance >= 2`, `class_balanced` (two selection rules for one
+    list), more than 1024 picks per image, heads wider than 256 classes, the full-size route (a model without `forward_lowres`,
+    FUSED_LOWRES switched off) and an image whose pool is smaller than `n_pixels_by_us`;
   * there is no CPU fallback: tensors must live on the GPU and the extension must be built.
 """
 import os
@@ -114,7 +124,11 @@ class QuerySelector:
         # not in the reference: the picks of an image round-robin over the predicted classes of its top_n_percent pool
         # (pp_class_balance_select) instead of the random sub-sample; absent / None / False = off
         self.class_balanced = bool(getattr(args, "class_balanced", False) or False)
+        # not in the reference: k-centre greedy selection over the class probabilities of the top_n_percent pool (pp_diverse_select)
+        # instead of the random sub-sample; absent / None / False = off
+        self.diverse_picks = bool(getattr(args, "diverse_picks", False) or False)
         self._check_balance()
+        self._check_diverse()
         self._check_bald()
         self._check_spread()
         self._check_region()
@@ -238,11 +252,63 @@ class QuerySelector:
             pred, _ = predict_lowres(low, full_size, crop=(h, w), align_corners=align, want_pred=True)
         return acq.class_balance_select(idx, pred, k, exclude=excl_dev)[0]
 
+    def _check_diverse(self, model=None):
+        """`diverse_picks` replaces the random sub-sample of the best `top_n_percent` by k-centre greedy selection over the class
+        probabilities of that pool; whatever has no such pool, no ranking or no single-pass probabilities is refused by name, never
+        served by another rule.  With a model (at the round): it must expose forward_lowres."""
+        if not getattr(self, "diverse_picks", False):
+            return
+        k = self.n_pixels_by_us
+        if not self.top_n_percent > 0.:
+            raise ValueError(f"diverse_picks cannot be combined with top_n_percent = {self.top_n_percent}: there is no pool to choose "
+                             f"from - with the n_pixels_by_us best pixels as the pool the rule returns plain top-k")
+        if self.reverse_order:
+            raise ValueError("diverse_picks cannot be combined with reverse_order: its candidate set is a random draw, not a ranked pool")
+        if self.query_strategy in ("random", "bald"):
+            raise ValueError(f"diverse_picks cannot be combined with query_strategy = {self.query_strategy!r}: the pool is the ranking of "
+                             f"a single-pass score (entropy, least_confidence, margin_sampling)")
+        if self.use_mc_dropout:
+            raise ValueError("diverse_picks cannot be combined with use_mc_dropout: the features of a committee of passes are not specified")
+        if self.min_pixel_distance >= 2:
+            raise ValueError(f"diverse_picks cannot be combined with min_pixel_distance = {self.min_pixel_distance}: two selection rules "
+                             f"for one list of candidates")
+        if self.class_balanced:
+            raise ValueError("diverse_picks cannot be combined with class_balanced: two selection rules for one list of candidates")
+        if k > acq.DIVERSE_MAX_PICKS:
+            raise ValueError(f"diverse_picks selects at most {acq.DIVERSE_MAX_PICKS} pixels per image: n_pixels_by_us = {k}")
+        if self.n_classes > acq.DIVERSE_MAX_FEATURES:
+            raise ValueError(f"diverse_picks takes one feature byte per class, at most {acq.DIVERSE_MAX_FEATURES}: n_classes = {self.n_classes}")
+        if model is not None and not (FUSED_LOWRES and hasattr(model, "forward_lowres")):
+            raise ValueError("diverse_picks takes the class probabilities from the classifier output: the model needs forward_lowres (and "
+                             "FUSED_LOWRES on); the full-size route is not served")
+
+    @property
+    def _diverse_on(self) -> bool:
+        return bool(getattr(self, "diverse_picks", False))
+
+    def _diverse(self, idx: torch.Tensor, low, full_size, excl_dev, h: int, w: int, align: bool) -> torch.Tensor:
+        """idx int32 [n,M] on the device, the rank-ordered pool of a *_topk launch at k = _k_launch -> the picks of the round
+        [n,n_pixels_by_us]: unchanged without diverse_picks, else pp_diverse_select's on the class probabilities
+        pp_acq_lowres_prob_at_u8 writes for the pool - still on the device, nothing read back in between."""
+        if not self._diverse_on:
+            return idx
+        k, (n, M) = self.n_pixels_by_us, idx.shape
+        if M < k:
+            raise ValueError(f"diverse_picks: the pool of a {h} x {w} image holds int(h*w*top_n_percent) = {M} candidates, fewer than "
+                             f"n_pixels_by_us = {k}")
+        C = int(low.shape[-1])
+        if C > acq.DIVERSE_MAX_FEATURES:
+            raise ValueError(f"diverse_picks takes one feature byte per class, at most {acq.DIVERSE_MAX_FEATURES}: the model has {C} classes")
+        img = torch.arange(n, dtype=torch.int32, device=idx.device).repeat_interleave(M)
+        feat = acq.prob_at_lowres(low, full_size, img, idx.reshape(-1), crop=(h, w), align_corners=align)
+        return acq.diverse_select(idx, feat.view(n, M, -1), k, n_features=C, exclude=excl_dev, n_pixels=h * w)[0]
+
     def _excl_arg(self, excl: np.ndarray):
-        """The exclusion mask as a scoring call takes it.  With min_pixel_distance, region_radius or class_balanced it is uploaded ONCE
-        here: the scorer and the selection read the same device bytes."""
+        """The exclusion mask as a scoring call takes it.  With min_pixel_distance, region_radius, class_balanced or diverse_picks it is
+        uploaded ONCE here: the scorer and the selection read the same device bytes."""
         t = torch.from_numpy(np.ascontiguousarray(excl))
-        return t.view(torch.uint8).to(self.device, non_blocking=True) if self._spread_on or self._region_on or self._balance_on else t
+        on_device = self._spread_on or self._region_on or self._balance_on or self._diverse_on
+        return t.view(torch.uint8).to(self.device, non_blocking=True) if on_device else t
 
     def _spread(self, idx: torch.Tensor, excl_dev, h: int, w: int) -> torch.Tensor:
         """idx int32 [n,M] on the device, rank-ordered (a *_topk launch at k = _k_launch) -> the picks of the round [n,n_pixels_by_us]:
@@ -375,7 +441,7 @@ class QuerySelector:
             d["rmap"] = rmap / np.float32(n_draws) if n_draws > 1 else rmap
         if self.reverse_order:
             d["cand"] = self._reverse_order_sampling_mask(h, w).reshape(h, w)                 # query.py:40
-        elif self.top_n_percent > 0. and not self._balance_on:         # class_balanced: the kernel chooses, nothing is drawn
+        elif self.top_n_percent > 0. and not (self._balance_on or self._diverse_on):   # class_balanced / diverse_picks: the kernel chooses, nothing is drawn
             # query.py:63-64 `np.random.choice(ind, n_pixels_by_us, False)`: numpy draws permutation(len)[:n] and indexes the
             # array with it, so drawing the POSITIONS consumes the same random numbers and picks the same pixels
             # (tests/test_host_logic.py) - and tells which of the read-back entropies belong to them
@@ -401,6 +467,7 @@ class QuerySelector:
             model.turn_on_dropout()
 
         self._check_balance(model)
+        self._check_diverse(model)
         self._check_bald()
         self._check_spread()
         self._check_region(model)
@@ -487,6 +554,7 @@ class QuerySelector:
                                                   align_corners=lowres_align)
             idx = self._spread(idx, excl_dev, h, w)            # min_pixel_distance: [n,M] -> [n,n_pixels_by_us], on the device
             idx = self._balance(idx, pred, low, full_size, excl_dev, h, w, lowres_align)      # class_balanced: likewise
+            idx = self._diverse(idx, low, full_size, excl_dev, h, w, lowres_align)             # diverse_picks: likewise
             n, k = idx.shape
             idx_host = torch.empty((n, k), dtype=torch.int32, pin_memory=True)
             idx_host.copy_(idx, non_blocking=True)
@@ -510,9 +578,9 @@ class QuerySelector:
             if pipelined and len({it.size for it in pending}) == 1:
                 launch_pipelined()
                 return
-            if (self._region_on or self._balance_on) and len({it.size for it in pending}) > 1:
+            if (self._region_on or self._balance_on or self._diverse_on) and len({it.size for it in pending}) > 1:
                 # equal padded shapes, different crops: one fused batch per size (the per-image routes below are neither region-scored
-                # nor class-balanced)
+                # nor class-balanced nor feature-diverse)
                 items = list(pending)
                 pending.clear()
                 for size in dict.fromkeys(it.size for it in items):
@@ -556,6 +624,7 @@ class QuerySelector:
                         idx, _, _ = acq.score_topk_lowres(low, full_size, excl_t, self.query_strategy,
                                                           self._k_launch(h, w), crop=(h, w), align_corners=lowres_align)
                     idx = self._balance(self._spread(idx, excl_t, h, w), pred, low, full_size, excl_t, h, w, lowres_align)
+                    idx = self._diverse(idx, low, full_size, excl_t, h, w, lowres_align)
                     idx_h = idx.cpu().numpy().astype(np.int64)
                 else:
                     excl_t = self._excl_arg(excl)
@@ -678,7 +747,7 @@ class QuerySelector:
         # strategy, reverse-order candidates, top-5 % sub-sample are drawn per image); for images of other ranks that only needs
         # (h, w), which the dataset provides as metadata (`image_sizes` / `image_size(i)`).  A dataset without it, in a mode that
         # draws, falls back to enumerating the whole loader and skipping.
-        needs_rng = is_random or self.reverse_order or (self.top_n_percent > 0. and not self._balance_on)
+        needs_rng = is_random or self.reverse_order or (self.top_n_percent > 0. and not (self._balance_on or self._diverse_on))
         sharded, sizes = None, None
         if world > 1 and getattr(self.dataloader, "batch_size", None) == 1:
             sizes = dist_utils.dataset_image_sizes(dataset)

@@ -1,7 +1,8 @@
 """Host-side functional API over the acquisition entry points of the C ABI.
 
 Everything here only marshals torch device tensors (pointers, strides, current stream) into
-include/pixelpick_hip.h calls; all arithmetic runs in the hand-written HIP kernels (csrc/acq.hip).
+include/pixelpick_hip.h calls; all arithmetic runs in the hand-written HIP kernels (csrc/acq.hip: the
+scorers and the ranking; csrc/acq_select.hip: the selectors that run after it).
 """
 from typing import Optional, Tuple
 
@@ -34,9 +35,8 @@ def _require_cuda_f32(t: torch.Tensor, name: str, ndim: int):
         raise ValueError(f"{name} must be float32, got {t.dtype}")
 
 
-def _exclude_u8(exclude, B, H, W, device):
-    if exclude is None:
-        return None
+def _mask_u8(exclude, device):
+    """An exclusion mask (numpy or tensor; bool, uint8 or anything compared with 0) as uint8 on the device, in its own shape."""
     if isinstance(exclude, np.ndarray):
         exclude = np.ascontiguousarray(exclude)       # also resolves negative strides (flipped views)
     ex = torch.as_tensor(exclude)
@@ -46,8 +46,42 @@ def _exclude_u8(exclude, B, H, W, device):
         ex = ex.contiguous().view(torch.uint8)
     elif ex.dtype != torch.uint8:
         ex = (ex != 0).contiguous().view(torch.uint8)
-    ex = ex.to(device, non_blocking=True).reshape(B, H, W).contiguous()
-    return ex
+    return ex.to(device, non_blocking=True)
+
+
+def _exclude_u8(exclude, B, H, W, device):
+    return None if exclude is None else _mask_u8(exclude, device).reshape(B, H, W).contiguous()
+
+
+# ---- the pool the selectors after the ranking work on: a rank-ordered list per image, an exclusion mask, idx / pos / n out ----
+def _pool_cand(cand):
+    """The list argument of every selector, int32 [B,M] on the GPU -> (cand contiguous, B, M, device)."""
+    if not isinstance(cand, torch.Tensor) or cand.ndim != 2 or cand.dtype != torch.int32:
+        raise ValueError("cand must be a 2-d int32 tensor [B,M]")
+    if not cand.is_cuda:
+        raise _lib.PixelPickHipError("cand must live on the GPU: the HIP path has no CPU fallback")
+    return (cand.contiguous(), *cand.shape, cand.device)
+
+
+def _pool_exclude(exclude, B, device, n_pixels=None, whose="n_pixels ="):
+    """The selectors' exclusion mask and pixel count -> (uint8 [B,N] on the device or None, N).  N is n_pixels where the caller knows
+    it (`whose` names its source in the message), else the mask's entries per image, else 2^31 - 1: no bound on the indices is known."""
+    N = None if n_pixels is None else int(n_pixels)
+    if exclude is None:
+        return None, 0x7FFFFFFF if N is None else N
+    ex = _mask_u8(exclude, device)
+    if ex.ndim == 0 or ex.shape[0] != B:
+        raise ValueError(f"exclude must be [B, ...] with B = {B} images, got {tuple(ex.shape)}")
+    ex = ex.reshape(B, -1).contiguous()
+    if N is not None and ex.shape[1] != N:
+        raise ValueError(f"exclude holds {ex.shape[1]} pixels per image, {whose} {N}")
+    return ex, ex.shape[1]
+
+
+def _pool_out(B, k, device, lists=2):
+    """`lists` int32 [B,k] tensors (idx, pos, ...) and n int32 [B] for a selector's picks."""
+    return [torch.empty((B, max(k, 0)), dtype=torch.int32, device=device) for _ in range(lists)] + \
+           [torch.empty((B,), dtype=torch.int32, device=device)]
 
 
 def _ws(nbytes: int, device) -> torch.Tensor:
@@ -458,34 +492,10 @@ def spread_select(cand: torch.Tensor, width: int, k: int, min_distance: int, exc
     exclude: [B, ...] with n_pixels entries per image, or None; n_pixels defaults to exclude's entries per image (without a mask: no
     bound on the indices is known, 2^31 - 1).  A candidate outside [0, n_pixels) counts as excluded.
     Returns (idx int32 [B,k], pos int32 [B,k] = list position of each pick, n int32 [B] = picks that satisfy the distance rule)."""
-    if not isinstance(cand, torch.Tensor) or cand.ndim != 2 or cand.dtype != torch.int32:
-        raise ValueError("cand must be a 2-d int32 tensor [B,M]")
-    if not cand.is_cuda:
-        raise _lib.PixelPickHipError("cand must live on the GPU: the HIP path has no CPU fallback")
-    cand = cand.contiguous()
-    B, M = cand.shape
-    dev = cand.device
-    ex = None
-    if exclude is not None:
-        if isinstance(exclude, np.ndarray):
-            exclude = np.ascontiguousarray(exclude)
-        ex = torch.as_tensor(exclude)
-        if ex.shape[0] != B:
-            raise ValueError(f"exclude holds {ex.shape[0]} images, cand {B}")
-        if ex.dtype == torch.bool:
-            ex = ex.contiguous().view(torch.uint8)
-        elif ex.dtype != torch.uint8:
-            ex = (ex != 0).contiguous().view(torch.uint8)
-        ex = ex.to(dev, non_blocking=True).reshape(B, -1).contiguous()
-        if n_pixels is None:
-            n_pixels = ex.shape[1]
-        elif ex.shape[1] != int(n_pixels):
-            raise ValueError(f"exclude holds {ex.shape[1]} pixels per image, n_pixels = {n_pixels}")
-    N = 0x7FFFFFFF if n_pixels is None else int(n_pixels)
+    cand, B, M, dev = _pool_cand(cand)
+    ex, N = _pool_exclude(exclude, B, dev, n_pixels)
     k = int(k)
-    idx = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
-    pos = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
-    n = torch.empty((B,), dtype=torch.int32, device=dev)
+    idx, pos, n = _pool_out(B, k, dev)
     with torch.cuda.device(dev):
         rc = _lib.lib().pp_spread_select(cand.data_ptr(), B, M, int(width), N, k, int(min_distance),
                                          ex.data_ptr() if ex is not None else None, idx.data_ptr(), pos.data_ptr(), n.data_ptr(),
@@ -495,7 +505,7 @@ def spread_select(cand: torch.Tensor, width: int, k: int, min_distance: int, exc
 
 
 # ---- region-aware acquisition: window impurity x window uncertainty (include/pixelpick_hip.h, pp_acq_region_score_map) ----
-REGION_TILE = (64, 64)         # (TH, TW) of region_score_kernel: one block per tile of one image (csrc/acq.hip, kRegionTH / kRegionTW)
+REGION_TILE = (64, 64)         # (TH, TW) of region_score_kernel: one block per tile of one image (csrc/acq_select.hip, kRegionTH / kRegionTW)
 REGION_MAX_RADIUS = 16
 REGION_MODE_ID = {"product": 0, "impurity": 1, "uncertainty": 2}
 REGION_FILL = -1.0             # at excluded pixels: 0.0 is the score of every pure window; the largest score wins in every mode
@@ -587,39 +597,17 @@ def class_balance_select(cand: torch.Tensor, label: torch.Tensor, k: int, exclud
     position): the best entry of every class in the pool first, then every class's second entry, and so on; a pool with fewer than
     k eligible entries is topped up with its earliest ineligible ones.  exclude: [B, ...] with the same N entries per image, or None.
     Returns (idx int32 [B,k], pos int32 [B,k] = list position of each pick, n int32 [B] = picks of the balanced phase)."""
-    if not isinstance(cand, torch.Tensor) or cand.ndim != 2 or cand.dtype != torch.int32:
-        raise ValueError("cand must be a 2-d int32 tensor [B,M]")
-    if not cand.is_cuda:
-        raise _lib.PixelPickHipError("cand must live on the GPU: the HIP path has no CPU fallback")
+    cand, B, M, dev = _pool_cand(cand)
     if not isinstance(label, torch.Tensor) or label.ndim < 2 or label.dtype != torch.uint8:
         raise ValueError("label must be a uint8 tensor [B, ...] (the label map predict_lowres writes)")
-    if not label.is_cuda or label.device != cand.device:
+    if not label.is_cuda or label.device != dev:
         raise _lib.PixelPickHipError("label must live on the GPU with cand: the HIP path has no CPU fallback")
-    cand = cand.contiguous()
-    B, M = cand.shape
-    dev = cand.device
     if label.shape[0] != B:
         raise ValueError(f"label holds {label.shape[0]} images, cand {B}")
     label = label.reshape(B, -1).contiguous()
-    N = label.shape[1]
-    ex = None
-    if exclude is not None:
-        if isinstance(exclude, np.ndarray):
-            exclude = np.ascontiguousarray(exclude)
-        ex = torch.as_tensor(exclude)
-        if ex.ndim < 2 or ex.shape[0] != B:
-            raise ValueError(f"exclude must be [B, ...] with B = {B}, got {tuple(ex.shape)}")
-        if ex.dtype == torch.bool:
-            ex = ex.contiguous().view(torch.uint8)
-        elif ex.dtype != torch.uint8:
-            ex = (ex != 0).contiguous().view(torch.uint8)
-        ex = ex.to(dev, non_blocking=True).reshape(B, -1).contiguous()
-        if ex.shape[1] != N:
-            raise ValueError(f"exclude holds {ex.shape[1]} pixels per image, label {N}")
+    ex, N = _pool_exclude(exclude, B, dev, label.shape[1], whose="label")
     k = int(k)
-    idx = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
-    pos = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
-    n = torch.empty((B,), dtype=torch.int32, device=dev)
+    idx, pos, n = _pool_out(B, k, dev)
     with torch.cuda.device(dev):
         rc = _lib.lib().pp_class_balance_select(cand.data_ptr(), B, M, N, k, label.data_ptr(), ex.data_ptr() if ex is not None else None,
                                                 idx.data_ptr(), pos.data_ptr(), n.data_ptr(), _lib.current_stream_ptr(dev))
@@ -668,17 +656,11 @@ def diverse_select(cand: torch.Tensor, feat: torch.Tensor, k: int, n_features: O
     exclude: [B, ...] with N entries per image, or None.  n_pixels: N, the pixels per image; None: that of exclude, and without
     exclude 2^31 - 1 (every non-negative index is inside).  Returns (idx int32 [B,k], pos int32 [B,k] = list position of each pick, dist int32 [B,k] = squared
     distance to the nearest earlier pick, -1 for pick 0 and the top-up, n int32 [B] = picks of the greedy phase)."""
-    if not isinstance(cand, torch.Tensor) or cand.ndim != 2 or cand.dtype != torch.int32:
-        raise ValueError("cand must be a 2-d int32 tensor [B,M]")
-    if not cand.is_cuda:
-        raise _lib.PixelPickHipError("cand must live on the GPU: the HIP path has no CPU fallback")
+    cand, B, M, dev = _pool_cand(cand)
     if not isinstance(feat, torch.Tensor) or feat.ndim != 3 or feat.dtype != torch.uint8:
         raise ValueError("feat must be a uint8 tensor [B,M,ldf] (the rows prob_at_lowres writes)")
-    if not feat.is_cuda or feat.device != cand.device:
+    if not feat.is_cuda or feat.device != dev:
         raise _lib.PixelPickHipError("feat must live on the GPU with cand: the HIP path has no CPU fallback")
-    cand = cand.contiguous()
-    B, M = cand.shape
-    dev = cand.device
     if feat.shape[0] != B:
         raise ValueError(f"feat holds {feat.shape[0]} images, cand {B}")
     if feat.shape[1] != M:
@@ -686,27 +668,10 @@ def diverse_select(cand: torch.Tensor, feat: torch.Tensor, k: int, n_features: O
     feat = feat.contiguous()
     ldf = feat.shape[2]
     F = ldf if n_features is None else int(n_features)
-    ex, N = None, 0x7FFFFFFF if n_pixels is None else int(n_pixels)
-    if exclude is not None:
-        if isinstance(exclude, np.ndarray):
-            exclude = np.ascontiguousarray(exclude)
-        ex = torch.as_tensor(exclude)
-        if ex.ndim < 2 or ex.shape[0] != B:
-            raise ValueError(f"exclude must be [B, ...] with B = {B}, got {tuple(ex.shape)}")
-        if ex.dtype == torch.bool:
-            ex = ex.contiguous().view(torch.uint8)
-        elif ex.dtype != torch.uint8:
-            ex = (ex != 0).contiguous().view(torch.uint8)
-        ex = ex.to(dev, non_blocking=True).reshape(B, -1).contiguous()
-        if n_pixels is not None and ex.shape[1] != N:
-            raise ValueError(f"exclude holds {ex.shape[1]} pixels per image, n_pixels = {N}")
-        N = ex.shape[1]
+    ex, N = _pool_exclude(exclude, B, dev, n_pixels)
     k = int(k)
     L = _lib.lib()
-    idx = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
-    pos = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
-    dist = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
-    n = torch.empty((B,), dtype=torch.int32, device=dev)
+    idx, pos, dist, n = _pool_out(B, k, dev, lists=3)
     ws = _ws(L.pp_diverse_workspace_bytes(B, M, F), dev)
     with torch.cuda.device(dev):
         rc = L.pp_diverse_select(cand.data_ptr(), B, M, N, k, feat.data_ptr(), F, ldf, ex.data_ptr() if ex is not None else None,

@@ -27,50 +27,51 @@ reference (`model.py:44,83`, `train.py:9,82`, `datasets/*.py` codecs) runs uncha
     or, on the full-size route (models without `forward_lowres`, chunked passes, heads wider than 64 classes), from the `prob` and
     mean entropy pp_acq_softmax_sum accumulates + pp_acq_mean_prob_score_map + pp_topk_select: no model is left out.  "bald"
     needs `use_mc_dropout` and is not a vote count: without MC-dropout, or with `vote_type="hard"`, it is a ValueError;
-  * `args.min_pixel_distance = d >= 2` (absent, 0 and 1: off, every path as before) spreads the picks of an image out: every scoring
-    route of a round launches with k = M = acquisition.spread_candidates(n_pixels_by_us, d, h*w) and hands its rank-ordered device
-    indices to pp_spread_select (include/pixelpick_hip.h), which walks them greedily and skips a candidate closer than d pixels to a
-    pick already taken - on the device, no RNG, equal to the greedy pass over the image's whole ranking.  It is the deterministic
-    alternative to the random sub-sample of the best `top_n_percent` (query.py:63-64) and refuses to be combined with it, with
-    `reverse_order` and with the `random` strategy;
-  * `args.region_radius = r` in [1, 16] (absent or 0: off, every path as before) ranks a pixel by its (2r+1)^2 neighbourhood instead of
-    its own class vector: the entropy of the predicted labels in the window times the window mean of the configured strategy's
-    uncertainty ("region impurity and prediction uncertainty"; `args.region_mode` = "product" (default) | "impurity" |
-    "uncertainty"; include/pixelpick_hip.h, pp_acq_region_score_map).  The two scoring branches that hold the classifier output -
-    the pipelined batch and the fused batch - then run pp_predict_lowres (label map), pp_acq_lowres_score_topk with k = 0 (score
-    map), pp_acq_region_score_map (the mask applied there; `margin_sampling` enters as 1 - margin, the largest score wins) and
-    pp_topk_select, all on the device with nothing new read back; `top_n_percent`, `reverse_order` and `min_pixel_distance` work
-    on its ranking as on any other.  Out of scope and REFUSED with a ValueError, never a silent fall-back: the MC-dropout routes
-    (`use_mc_dropout`, "bald"), the `random` strategy, heads wider than 256 classes and the full-size route (a model without
-    `forward_lowres`, FUSED_LOWRES switched off);
-  * `args.class_balanced` (absent, None and False: off, every path as before, the host RNG streams included) replaces the random
-    sub-sample of the best `top_n_percent` (query.py:63-64), which is blind to classes, by a deterministic rule: the pool stays the
-    reference's - M = int(h*w*top_n_percent) rank-ordered candidates per image - and pp_class_balance_select (include/pixelpick_hip.h)
-    hands the n_pixels_by_us picks out round-robin over the PREDICTED classes in it: the best entry of every class first, then every
-    class's second entry, and so on.  The pipelined batch and the fused batch run pp_predict_lowres (the label map; with
-    `region_radius` the one the region score already made) and the selection on the device, nothing new is read back and no
-    position is drawn from numpy's stream.  It works on the region ranking as on any other.  REFUSED with a ValueError, never a
-    silent fall-back: `top_n_percent <= 0` (no pool), `reverse_order`, the `random` and "bald" strategies, `use_mc_dropout`,
-    `min_pixel_distance >= 2`, more than 1024 picks per image, heads wider than 256 classes, the full-size route (a model without
-    `forward_lowres`, FUSED_LOWRES switched off) and an image whose pool is smaller than `n_pixels_by_us`;
-  * `args.diverse_picks` (absent, None and False: off, every path as before, the host RNG streams included) replaces the random
-    sub-sample of the best `top_n_percent` (query.py:63-64) by core-set / k-centre greedy selection in the model's own output space:
-    the pool stays the reference's - M = int(h*w*top_n_percent) rank-ordered candidates per image - pp_acq_lowres_prob_at_u8 writes
-    every candidate's class probabilities as bytes and pp_diverse_select (include/pixelpick_hip.h) takes the pool's most uncertain
-    pixel first, then n_pixels_by_us - 1 times the candidate farthest from the picks so far.  The pipelined batch and the fused batch
-    run both on the device, nothing new is read back and no position is drawn from numpy's stream.  It works on the region ranking
-    as on any other.  REFUSED with a ValueError, never a silent fall-back: `top_n_percent <= 0` (no pool), `reverse_order`, the
-    `random` and "bald" strategies, `use_mc_dropout`, `min_pixel_distance >= 2`, `class_balanced` (two selection rules for one
-    list), more than 1024 picks per image, heads wider than 256 classes, the full-size route (a model without `forward_lowres`,
-    FUSED_LOWRES switched off) and an image whose pool is smaller than `n_pixels_by_us`;
   * there is no CPU fallback: tensors must live on the GPU and the extension must be built.
+
+Four options that are not in the reference act after the ranking (csrc/acq_select.hip).  Each is off when absent, None, 0 or False, and
+every path, the host RNG streams included, is then as before.  The batch routes that hold the classifier output - the pipelined batch
+and the one-launch batch - run them on the device in this order, with nothing new read back (QuerySelector._device_picks):
+
+  * `args.region_radius = r` in [1, 16] ranks a pixel by its (2r+1)^2 neighbourhood instead of its own class vector: the entropy of
+    the predicted labels in the window times the window mean of the configured strategy's uncertainty (`args.region_mode` =
+    "product" (default) | "impurity" | "uncertainty"): pp_predict_lowres (label map), pp_acq_lowres_score_topk with k = 0 (score
+    map), pp_acq_region_score_map (the mask applied there; `margin_sampling` enters as 1 - margin, the largest score wins) and
+    pp_topk_select.  `top_n_percent`, `reverse_order` and the three rules below work on its ranking as on any other;
+  * `args.min_pixel_distance = d >= 2` (1 is off as well) spreads the picks of an image out: every scoring route of a round launches
+    with k = M = acquisition.spread_candidates(n_pixels_by_us, d, h*w) and pp_spread_select walks that list greedily, skipping a
+    candidate closer than d pixels to a pick already taken - equal to the greedy pass over the image's whole ranking;
+  * `args.class_balanced` and `args.diverse_picks` replace the random sub-sample of the best `top_n_percent` (query.py:63-64).  The
+    pool stays the reference's - M = int(h*w*top_n_percent) rank-ordered candidates per image - and no position is drawn from
+    numpy's stream.  `class_balanced`: pp_class_balance_select hands the picks out round-robin over the PREDICTED classes in the pool
+    (pp_predict_lowres' label map; with `region_radius` the one the region score already made).  `diverse_picks`: k-centre greedy in
+    the model's output space: pp_acq_lowres_prob_at_u8 writes every candidate's class probabilities as bytes and pp_diverse_select
+    takes the pool's best pixel first, then n_pixels_by_us - 1 times the candidate farthest from the picks so far.
+
+What an option cannot serve is REFUSED with a ValueError that names it, at construction and again at the round, never replaced by
+another rule (QuerySelector._check_*):
+
+  ============================================  ======  ======  ==========================
+  combined with                                 region  spread  class_balanced / diverse
+  ============================================  ======  ======  ==========================
+  `random` strategy                             x       x       x
+  "bald"; `use_mc_dropout`                      x               x
+  `reverse_order`                                       x       x
+  `top_n_percent` > 0 / <= 0                            > 0     <= 0 (no pool)
+  `min_pixel_distance` >= 2; each other                         x
+  more than 1024 picks per image                        x       x
+  heads wider than 256 classes                  x               x
+  the full-size route (no `forward_lowres`,     x               x
+  FUSED_LOWRES off)
+  an image whose pool is smaller than k                         x
+  ============================================  ======  ======  ==========================
 """
 import os
 import pickle as pkl
 import warnings
 from math import ceil
 from pathlib import Path
-from typing import Dict, List, Tuple, Union
+from typing import Callable, Dict, List, NamedTuple, Tuple, Union
 
 import numpy as np
 import torch
@@ -86,6 +87,46 @@ FUSED_LOWRES = os.environ.get("PIXELPICK_FUSED_LOWRES", "1") != "0"
 # PIXELPICK_QUERY_PIPELINE=0: finish every batch of an acquisition round (index / entropy read-back, masks, statistics)
 # before the next one is loaded, instead of doing that host work while the GPU already runs the next batch
 QUERY_PIPELINE = os.environ.get("PIXELPICK_QUERY_PIPELINE", "1") != "0"
+
+
+def _need_lowres(option: str, model):
+    """region_radius, class_balanced and diverse_picks work on the classifier output (`model` None: construction, nothing to check)."""
+    if model is not None and not (FUSED_LOWRES and hasattr(model, "forward_lowres")):
+        raise ValueError(f"{option} works on the classifier output: the model needs forward_lowres (and FUSED_LOWRES on); the "
+                         f"full-size route is not served")
+
+
+def _need_byte_classes(option: str, n: int, cap: int = 256, what: str = "n_classes"):
+    """The same three keep one byte per class: a label map of bytes, a feature row of one byte per class."""
+    if n > cap:
+        raise ValueError(f"{option} keeps one byte per class (label map, feature row), at most {cap} classes: {what} = {n}")
+
+
+def _select_balanced(idx, k, excl_dev, label_map, **_):
+    return acq.class_balance_select(idx, label_map(), k, exclude=excl_dev)[0]
+
+
+def _select_diverse(idx, k, excl_dev, low, full_size, crop, n_pixels, **_):
+    n, M = idx.shape
+    img = torch.arange(n, dtype=torch.int32, device=idx.device).repeat_interleave(M)
+    feat = acq.prob_at_lowres(low, full_size, img, idx.reshape(-1), **crop)
+    return acq.diverse_select(idx, feat.view(n, M, -1), k, n_features=int(low.shape[-1]), exclude=excl_dev, n_pixels=n_pixels)[0]
+
+
+class _PoolRule(NamedTuple):
+    """A rule that replaces the random sub-sample of the top_n_percent pool: the option, the nouns of its refusals (what there is no
+    pool to do, what a committee of MC-dropout passes leaves unspecified), its caps and its step of QuerySelector._device_picks:
+    select(idx [n,M], k, excl_dev, low=, full_size=, crop=, n_pixels=, label_map=) -> picks [n,k]."""
+    option: str
+    pool_for: str
+    committee: str
+    max_picks: int
+    max_classes: int
+    select: Callable
+
+
+_POOL_RULES = (_PoolRule("class_balanced", "balance", "label", acq.BALANCE_MAX_PICKS, 256, _select_balanced),
+               _PoolRule("diverse_picks", "choose from", "features", acq.DIVERSE_MAX_PICKS, acq.DIVERSE_MAX_FEATURES, _select_diverse))
 
 
 class QuerySelector:
@@ -127,11 +168,14 @@ class QuerySelector:
         # not in the reference: k-centre greedy selection over the class probabilities of the top_n_percent pool (pp_diverse_select)
         # instead of the random sub-sample; absent / None / False = off
         self.diverse_picks = bool(getattr(args, "diverse_picks", False) or False)
-        self._check_balance()
-        self._check_diverse()
+        self._check_options()
+
+    def _check_options(self, model=None):
+        """Every refusal, at construction and (with the model) again at the round."""
+        self._check_pool_rules(model)
         self._check_bald()
         self._check_spread()
-        self._check_region()
+        self._check_region(model)
 
     def _check_bald(self):
         """`bald` is the mutual information between the prediction and the dropout mask: it exists only over stochastic passes, and
@@ -180,128 +224,51 @@ class QuerySelector:
                              f"uncertainty is the mean of a single-pass score map (entropy, least_confidence, margin_sampling)")
         if self.use_mc_dropout:
             raise ValueError(f"region_radius = {r} cannot be combined with use_mc_dropout: the MC-dropout routes are not region-scored")
-        if self.n_classes > 256:
-            raise ValueError(f"region_radius = {r} needs a label map of bytes: n_classes = {self.n_classes} > 256")
-        if model is not None and not (FUSED_LOWRES and hasattr(model, "forward_lowres")):
-            raise ValueError(f"region_radius = {r} is scored from the classifier output: the model needs forward_lowres (and FUSED_LOWRES "
-                             f"on); the full-size route is not region-scored")
+        _need_byte_classes(f"region_radius = {r}", self.n_classes)
+        _need_lowres(f"region_radius = {r}", model)
 
     @property
     def _region_on(self) -> bool:
         return self.region_radius >= 1
 
-    def _region_topk(self, low, full_size, excl_dev, h: int, w: int, align: bool) -> Tuple[torch.Tensor, torch.Tensor]:
-        """The region-scored replacement of one score_topk_lowres launch: label map + score map of the configured strategy (no mask) ->
-        window impurity x window uncertainty with the mask applied -> top-k, the largest first.  -> (int32 [n,_k_launch], the label
-        map uint8 [n,h,w] it was scored from - class_balanced reads the same one), both on the device."""
-        C = int(low.shape[-1])
-        if C > 256:
-            raise ValueError(f"region_radius = {self.region_radius} needs a label map of bytes: the model has {C} classes")
-        pred, _ = predict_lowres(low, full_size, crop=(h, w), align_corners=align, want_pred=True)
-        _, _, unc = acq.score_topk_lowres(low, full_size, None, self.query_strategy, 0, crop=(h, w), align_corners=align)
-        rmap = acq.region_score_map(pred, unc, self.region_radius, C, exclude=excl_dev, mode=self.region_mode,
-                                    flip=not acq.LARGEST[self.query_strategy])
-        return acq.topk_select(rmap.reshape(rmap.shape[0], h * w), self._k_launch(h, w), True)[0], pred
+    def _pool_rules(self) -> list:
+        return [rule for rule in _POOL_RULES if getattr(self, rule.option, False)]
 
-    def _check_balance(self, model=None):
-        """`class_balanced` replaces the random sub-sample of the best `top_n_percent` by the round-robin over the predicted classes of
-        that pool; whatever has no such pool, no ranking or no single-pass label map is refused by name, never served by another
-        rule.  With a model (at the round): it must expose forward_lowres."""
-        if not self.class_balanced:
-            return
-        k = self.n_pixels_by_us
-        if not self.top_n_percent > 0.:
-            raise ValueError(f"class_balanced cannot be combined with top_n_percent = {self.top_n_percent}: there is no pool to balance - "
-                             f"with the n_pixels_by_us best pixels as the pool the rule returns plain top-k")
-        if self.reverse_order:
-            raise ValueError("class_balanced cannot be combined with reverse_order: its candidate set is a random draw, not a ranked pool")
-        if self.query_strategy in ("random", "bald"):
-            raise ValueError(f"class_balanced cannot be combined with query_strategy = {self.query_strategy!r}: the pool is the ranking of "
-                             f"a single-pass score (entropy, least_confidence, margin_sampling)")
-        if self.use_mc_dropout:
-            raise ValueError("class_balanced cannot be combined with use_mc_dropout: the label of a committee of passes is not specified")
-        if self.min_pixel_distance >= 2:
-            raise ValueError(f"class_balanced cannot be combined with min_pixel_distance = {self.min_pixel_distance}: two selection rules "
-                             f"for one list of candidates")
-        if k > acq.BALANCE_MAX_PICKS:
-            raise ValueError(f"class_balanced selects at most {acq.BALANCE_MAX_PICKS} pixels per image: n_pixels_by_us = {k}")
-        if self.n_classes > 256:
-            raise ValueError(f"class_balanced needs a label map of bytes: n_classes = {self.n_classes} > 256")
-        if model is not None and not (FUSED_LOWRES and hasattr(model, "forward_lowres")):
-            raise ValueError("class_balanced takes the label map from the classifier output: the model needs forward_lowres (and "
-                             "FUSED_LOWRES on); the full-size route is not class-balanced")
+    def _check_pool_rules(self, model=None):
+        """`class_balanced` / `diverse_picks` replace the random sub-sample of the best `top_n_percent` by a rule over that pool;
+        whatever has no such pool, no ranking or no single-pass classifier output is refused by name, never served by another rule.
+        With a model (at the round): it must expose forward_lowres."""
+        on = self._pool_rules()
+        for rule in on:
+            name, k = rule.option, self.n_pixels_by_us
+            if not self.top_n_percent > 0.:
+                raise ValueError(f"{name} cannot be combined with top_n_percent = {self.top_n_percent}: there is no pool to "
+                                 f"{rule.pool_for} - with the n_pixels_by_us best pixels as the pool the rule returns plain top-k")
+            if self.reverse_order:
+                raise ValueError(f"{name} cannot be combined with reverse_order: its candidate set is a random draw, not a ranked pool")
+            if self.query_strategy in ("random", "bald"):
+                raise ValueError(f"{name} cannot be combined with query_strategy = {self.query_strategy!r}: the pool is the ranking of "
+                                 f"a single-pass score (entropy, least_confidence, margin_sampling)")
+            if self.use_mc_dropout:
+                raise ValueError(f"{name} cannot be combined with use_mc_dropout: the {rule.committee} of a committee of passes "
+                                 f"{'is' if rule.committee == 'label' else 'are'} not specified")
+            if self.min_pixel_distance >= 2:
+                raise ValueError(f"{name} cannot be combined with min_pixel_distance = {self.min_pixel_distance}: two selection rules "
+                                 f"for one list of candidates")
+            if rule is not on[0]:
+                raise ValueError(f"{name} cannot be combined with {on[0].option}: two selection rules for one list of candidates")
+            if k > rule.max_picks:
+                raise ValueError(f"{name} selects at most {rule.max_picks} pixels per image: n_pixels_by_us = {k}")
+            _need_byte_classes(name, self.n_classes, rule.max_classes)
+            _need_lowres(name, model)
 
     @property
     def _balance_on(self) -> bool:
-        return bool(self.class_balanced)
-
-    def _balance(self, idx: torch.Tensor, pred, low, full_size, excl_dev, h: int, w: int, align: bool) -> torch.Tensor:
-        """idx int32 [n,M] on the device, the rank-ordered pool of a *_topk launch at k = _k_launch -> the picks of the round
-        [n,n_pixels_by_us]: unchanged without class_balanced, else pp_class_balance_select's on the label map `pred` (made here by
-        pp_predict_lowres unless the region score already made it) - still on the device, nothing read back in between."""
-        if not self._balance_on:
-            return idx
-        k, M = self.n_pixels_by_us, int(idx.shape[1])
-        if M < k:
-            raise ValueError(f"class_balanced: the pool of a {h} x {w} image holds int(h*w*top_n_percent) = {M} candidates, fewer than "
-                             f"n_pixels_by_us = {k}")
-        if pred is None:
-            C = int(low.shape[-1])
-            if C > 256:
-                raise ValueError(f"class_balanced needs a label map of bytes: the model has {C} classes")
-            pred, _ = predict_lowres(low, full_size, crop=(h, w), align_corners=align, want_pred=True)
-        return acq.class_balance_select(idx, pred, k, exclude=excl_dev)[0]
-
-    def _check_diverse(self, model=None):
-        """`diverse_picks` replaces the random sub-sample of the best `top_n_percent` by k-centre greedy selection over the class
-        probabilities of that pool; whatever has no such pool, no ranking or no single-pass probabilities is refused by name, never
-        served by another rule.  With a model (at the round): it must expose forward_lowres."""
-        if not getattr(self, "diverse_picks", False):
-            return
-        k = self.n_pixels_by_us
-        if not self.top_n_percent > 0.:
-            raise ValueError(f"diverse_picks cannot be combined with top_n_percent = {self.top_n_percent}: there is no pool to choose "
-                             f"from - with the n_pixels_by_us best pixels as the pool the rule returns plain top-k")
-        if self.reverse_order:
-            raise ValueError("diverse_picks cannot be combined with reverse_order: its candidate set is a random draw, not a ranked pool")
-        if self.query_strategy in ("random", "bald"):
-            raise ValueError(f"diverse_picks cannot be combined with query_strategy = {self.query_strategy!r}: the pool is the ranking of "
-                             f"a single-pass score (entropy, least_confidence, margin_sampling)")
-        if self.use_mc_dropout:
-            raise ValueError("diverse_picks cannot be combined with use_mc_dropout: the features of a committee of passes are not specified")
-        if self.min_pixel_distance >= 2:
-            raise ValueError(f"diverse_picks cannot be combined with min_pixel_distance = {self.min_pixel_distance}: two selection rules "
-                             f"for one list of candidates")
-        if self.class_balanced:
-            raise ValueError("diverse_picks cannot be combined with class_balanced: two selection rules for one list of candidates")
-        if k > acq.DIVERSE_MAX_PICKS:
-            raise ValueError(f"diverse_picks selects at most {acq.DIVERSE_MAX_PICKS} pixels per image: n_pixels_by_us = {k}")
-        if self.n_classes > acq.DIVERSE_MAX_FEATURES:
-            raise ValueError(f"diverse_picks takes one feature byte per class, at most {acq.DIVERSE_MAX_FEATURES}: n_classes = {self.n_classes}")
-        if model is not None and not (FUSED_LOWRES and hasattr(model, "forward_lowres")):
-            raise ValueError("diverse_picks takes the class probabilities from the classifier output: the model needs forward_lowres (and "
-                             "FUSED_LOWRES on); the full-size route is not served")
+        return bool(getattr(self, "class_balanced", False))
 
     @property
     def _diverse_on(self) -> bool:
         return bool(getattr(self, "diverse_picks", False))
-
-    def _diverse(self, idx: torch.Tensor, low, full_size, excl_dev, h: int, w: int, align: bool) -> torch.Tensor:
-        """idx int32 [n,M] on the device, the rank-ordered pool of a *_topk launch at k = _k_launch -> the picks of the round
-        [n,n_pixels_by_us]: unchanged without diverse_picks, else pp_diverse_select's on the class probabilities
-        pp_acq_lowres_prob_at_u8 writes for the pool - still on the device, nothing read back in between."""
-        if not self._diverse_on:
-            return idx
-        k, (n, M) = self.n_pixels_by_us, idx.shape
-        if M < k:
-            raise ValueError(f"diverse_picks: the pool of a {h} x {w} image holds int(h*w*top_n_percent) = {M} candidates, fewer than "
-                             f"n_pixels_by_us = {k}")
-        C = int(low.shape[-1])
-        if C > acq.DIVERSE_MAX_FEATURES:
-            raise ValueError(f"diverse_picks takes one feature byte per class, at most {acq.DIVERSE_MAX_FEATURES}: the model has {C} classes")
-        img = torch.arange(n, dtype=torch.int32, device=idx.device).repeat_interleave(M)
-        feat = acq.prob_at_lowres(low, full_size, img, idx.reshape(-1), crop=(h, w), align_corners=align)
-        return acq.diverse_select(idx, feat.view(n, M, -1), k, n_features=C, exclude=excl_dev, n_pixels=h * w)[0]
 
     def _excl_arg(self, excl: np.ndarray):
         """The exclusion mask as a scoring call takes it.  With min_pixel_distance, region_radius, class_balanced or diverse_picks it is
@@ -316,6 +283,41 @@ class QuerySelector:
         if not self._spread_on:
             return idx
         return acq.spread_select(idx, w, self.n_pixels_by_us, self.min_pixel_distance, exclude=excl_dev, n_pixels=h * w)[0]
+
+    def _device_picks(self, low, full_size, excl_dev, h: int, w: int, align: bool) -> torch.Tensor:
+        """The device chain of the batch routes: the classifier output `low` of n images of crop h x w and their exclusion mask on the
+        device -> the picks of the round int32 [n,k] (k = n_pixels_by_us; without a rule after the ranking, _k_launch), on the device,
+        nothing read back in between.  The ranking (region-scored: label map + score map of the strategy without the mask -> window
+        impurity x window uncertainty with the mask -> top-k, the largest first; else the scorer), then min_pixel_distance, then
+        class_balanced (on the region's label map where there is one) or diverse_picks."""
+        crop = dict(crop=(h, w), align_corners=align)
+        C, pred = int(low.shape[-1]), None
+
+        def label_map():                # one pp_predict_lowres launch per batch, whoever asks first
+            nonlocal pred
+            if pred is None:
+                pred = predict_lowres(low, full_size, want_pred=True, **crop)[0]
+            return pred
+
+        if self._region_on:
+            _need_byte_classes(f"region_radius = {self.region_radius}", C, what="the model's classes")
+            pred = label_map()
+            _, _, unc = acq.score_topk_lowres(low, full_size, None, self.query_strategy, 0, **crop)
+            rmap = acq.region_score_map(pred, unc, self.region_radius, C, exclude=excl_dev, mode=self.region_mode,
+                                        flip=not acq.LARGEST[self.query_strategy])
+            idx = acq.topk_select(rmap.reshape(rmap.shape[0], h * w), self._k_launch(h, w), True)[0]
+        else:
+            idx = acq.score_topk_lowres(low, full_size, excl_dev, self.query_strategy, self._k_launch(h, w), **crop)[0]
+        idx = self._spread(idx, excl_dev, h, w)
+        for rule in self._pool_rules():
+            k, (n, M) = self.n_pixels_by_us, idx.shape
+            if M < k:
+                raise ValueError(f"{rule.option}: the pool of a {h} x {w} image holds int(h*w*top_n_percent) = {M} candidates, fewer "
+                                 f"than n_pixels_by_us = {k}")
+            _need_byte_classes(rule.option, C, rule.max_classes, what="the model's classes")
+            idx = rule.select(idx, k, excl_dev, low=low, full_size=full_size, crop=crop, n_pixels=h * w, label_map=label_map)
+        return idx
+
 
     # ------------------------------------------------------------------ selection (query.py:33-69)
     @property
@@ -453,6 +455,269 @@ class QuerySelector:
             return acq.spread_candidates(self.n_pixels_by_us, self.min_pixel_distance, h * w)
         return self.n_pixels_by_us if self.reverse_order else self._k_topk(h, w)
 
+    def _plan_round(self, model, human_labels: bool) -> "_Round":
+        """What a round decides once, before the loader loop: which scoring route its batches take."""
+        is_random = self.query_strategy == "random"
+        has_lowres = hasattr(model, "forward_lowres")
+        rd = _Round(model, human_labels)
+        # Low-resolution scoring, no reverse-order sampling: the GPU work of a batch is only ENQUEUED by _flush(); its results
+        # come back through pinned buffers and are turned into masks / statistics after the next batch has been loaded and
+        # enqueued, so host and GPU overlap.
+        rd.pipelined = (QUERY_PIPELINE and FUSED_LOWRES and not self.use_mc_dropout and has_lowres
+                        and not self.reverse_order and not is_random and torch.device(self.device).type == "cuda")
+        # MC-dropout (query.py:177-187) scored from the classifier output of all passes (pp_acq_lowres_mc_score_topk); chunked
+        # passes, the random strategy, models without forward_lowres and heads wider than the kernel keep the full-size route
+        rd.mc_lowres = (FUSED_LOWRES and self.use_mc_dropout and has_lowres and not is_random
+                        and self.mc_n_steps <= self.mc_chunk
+                        and int(getattr(model, "n_classes", self.n_classes)) <= acq.MC_LOWRES_MAX_CLASSES)
+        # DeepLab: x4 align_corners=True (deeplab.py:55-56); FPNSeg: x2 align_corners=False (decoders.py:101)
+        rd.lowres_align = bool(getattr(model, "LOWRES_ALIGN_CORNERS", True))
+        # the strategy on the mean probability of the passes (vote_type="consensus"), or their mutual information ("bald")
+        rd.mean_vote = self.use_mc_dropout and not is_random and (self.query_strategy == "bald" or self.vote_type == "consensus")
+        # args.py:34: the passes vote with their arg-max class and the strategy scores the vote shares (never a silent soft vote)
+        rd.hard_vote = self.use_mc_dropout and self.vote_type == "hard" and not is_random
+        if rd.hard_vote and not has_lowres:
+            # the vote is specified on pp_bilinear_fwd's logits; the picks of other models are pinned to the mean score
+            warnings.warn("vote_type='hard' needs a model with forward_lowres: this round uses the mean score (soft vote)", RuntimeWarning)
+            rd.hard_vote = False
+        if rd.hard_vote and not 1 <= self.mc_n_steps <= acq.MC_VOTE_MAX_PASSES:
+            raise ValueError(f"vote_type='hard' counts the votes in bytes: mc_n_steps = {self.mc_n_steps} is outside "
+                             f"[1, {acq.MC_VOTE_MAX_PASSES}]")
+        rd.copy_stream = self.__dict__.get("_copy_stream")
+        if rd.pipelined and rd.copy_stream is None:
+            rd.copy_stream = self.__dict__["_copy_stream"] = torch.cuda.Stream(device=self.device)
+        return rd
+
+    @staticmethod
+    def _emit(rd, it, cand, cand_ent):
+        """cand: the chosen flat indices of image `it` (any order), cand_ent: their entropies in the same order | None."""
+        h, w = it.size
+        order = np.argsort(cand, kind="stable")
+        sel = np.asarray(cand, dtype=np.int64)[order]
+        contrib = None
+        if cand_ent is not None:
+            contrib = QueryStats.contribution(it.y, np.asarray(cand_ent)[order].tolist(), (sel // w, sel % w))
+        rd.records.append((it.index, it.p_img, h, w, sel, contrib))
+
+    @staticmethod
+    def _drawn(it, idx_sorted, ent_sorted=None):
+        """query.py:63-64 on the value-sorted top-k of one image -> (flat indices, their entropies | None)."""
+        pos = it.draws.get("pos")
+        if pos is not None:
+            return idx_sorted[pos], (ent_sorted[pos] if ent_sorted is not None else None)
+        return idx_sorted, ent_sorted
+
+    def _emit_with_stats(self, rd, it, cand, row_major_entropy):
+        """The per-image routes' tail: row_major_entropy(bool mask [h,w]) -> the entropies at the picks in ascending flat index,
+        re-ordered here to the order of `cand`; not asked for when the round keeps no statistics."""
+        ent = None
+        if not rd.human_labels and it.y is not None:
+            h, w = it.size
+            qmask = np.zeros(h * w, dtype=np.bool_)
+            qmask[cand] = True
+            ent = np.empty(len(cand), dtype=np.float64)
+            ent[np.argsort(cand, kind="stable")] = row_major_entropy(qmask.reshape(h, w))
+        self._emit(rd, it, cand, ent)
+
+    def _flush(self, rd):
+        """Score the pending images (equal padded shapes) by the route of the round and empty the list."""
+        pending = rd.pending
+        if not pending:
+            return
+        sizes = dict.fromkeys(it.size for it in pending)
+        if rd.pipelined and len(sizes) == 1:
+            self._launch_pipelined(rd)
+            return
+        if (self._region_on or self._balance_on or self._diverse_on) and len(sizes) > 1:
+            # equal padded shapes, different crops: one batch per crop (the per-image routes are neither region-scored nor
+            # class-balanced nor feature-diverse)
+            items = list(pending)
+            pending.clear()
+            for size in sizes:
+                pending.extend(it for it in items if it.size == size)
+                self._flush(rd)
+            return
+        if rd.inflight:
+            self._finish_pipelined(rd, rd.inflight.pop())
+        if rd.pipelined:                                       # images were uploaded (and voc-padded) on copy_stream
+            main = torch.cuda.current_stream(self.device)
+            main.wait_stream(rd.copy_stream)
+            for it in pending:
+                it.x.record_stream(main)
+        if not self.use_mc_dropout and len(sizes) == 1:
+            self._score_batch(rd)
+        elif rd.mc_lowres:
+            self._score_mc_lowres(rd)
+        else:
+            self._score_per_image(rd)
+        pending.clear()
+
+    def _launch_pipelined(self, rd):
+        """The pipelined batch: enqueue everything, read back through pinned buffers, finish the PREVIOUS batch meanwhile."""
+        pending, model, align = rd.pending, rd.model, rd.lowres_align
+        (h, w), = {it.size for it in pending}
+        main = torch.cuda.current_stream(self.device)
+        excl = np.ascontiguousarray(np.stack([it.exclude for it in pending]))
+        with torch.cuda.stream(rd.copy_stream):                # a pageable upload on the main stream would block the host
+            excl_dev = torch.from_numpy(excl).view(torch.uint8).to(self.device)    # behind everything enqueued there
+        main.wait_stream(rd.copy_stream)                       # images and exclusion masks of this batch have arrived
+        excl_dev.record_stream(main)
+        xs = torch.cat([it.x for it in pending], dim=0)
+        for it in pending:
+            it.x.record_stream(main)
+        low, full_size = model.forward_lowres(xs)
+        idx = self._device_picks(low, full_size, excl_dev, h, w, align)
+        n, k = idx.shape
+        idx_host = torch.empty((n, k), dtype=torch.int32, pin_memory=True)
+        idx_host.copy_(idx, non_blocking=True)
+        ent_host = None
+        if not rd.human_labels and all(it.y is not None for it in pending):
+            img = torch.arange(n, device=idx.device, dtype=torch.int32).repeat_interleave(k)
+            ent = acq.score_at_lowres(low, full_size, img, idx.reshape(-1), "entropy", crop=(h, w), align_corners=align)
+            ent_host = torch.empty((n, k), dtype=torch.float32, pin_memory=True)
+            ent_host.copy_(ent.reshape(n, k), non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(main)
+        handle = (list(pending), idx_host, ent_host, ev)
+        pending.clear()
+        if rd.inflight:
+            self._finish_pipelined(rd, rd.inflight.pop())      # the PREVIOUS batch, while the GPU works on this one
+        rd.inflight.append(handle)
+
+    def _finish_pipelined(self, rd, handle):
+        """Host half of a pipelined batch: wait for ITS read-back (not for whatever the GPU runs now)."""
+        items, idx_host, ent_host, ev = handle
+        ev.synchronize()
+        idx_h = idx_host.numpy().astype(np.int64)
+        ent_h = ent_host.numpy() if ent_host is not None else None
+        for j, it in enumerate(items):
+            self._emit(rd, it, *self._drawn(it, idx_h[j], ent_h[j] if ent_h is not None else None))
+
+    def _score_batch(self, rd):
+        """The one-launch batch (no MC-dropout, one crop): one scoring launch, one index read-back and one entropy read-back."""
+        pending, model, align = rd.pending, rd.model, rd.lowres_align
+        (h, w), = {it.size for it in pending}
+        xs = torch.cat([it.x for it in pending], dim=0)
+        # SURVEY.md §8f rank 1: DeepLab exposes its classifier output in front of the x4 upsample; the scoring
+        # kernel interpolates on the fly and the full-resolution logits are never written
+        fused = FUSED_LOWRES and hasattr(model, "forward_lowres")
+        if fused:
+            low, full_size = model.forward_lowres(xs)
+        else:
+            lg = model(xs)["pred"][:, :, :h, :w]
+        excl = np.stack([it.exclude for it in pending])
+        if self.reverse_order:
+            excl = excl | ~np.stack([it.draws["cand"] for it in pending])
+        if self.query_strategy == "random":
+            # the forward above only feeds the statistics (the reference runs it too, query.py:190)
+            idx_h = self._random_topk(np.stack([it.draws["rmap"] for it in pending]), excl, self._k_launch(h, w))
+        elif fused:
+            idx_h = self._device_picks(low, full_size, self._excl_arg(excl), h, w, align).cpu().numpy().astype(np.int64)
+        else:
+            excl_t = self._excl_arg(excl)
+            idx, _, _ = acq.score_topk(lg, excl_t, self.query_strategy, self._k_launch(h, w))
+            idx_h = self._spread(idx, excl_t, h, w).cpu().numpy().astype(np.int64)
+        chosen = [self._drawn(it, idx_h[j])[0] for j, it in enumerate(pending)]
+        want_stats = (not rd.human_labels) and all(it.y is not None for it in pending)
+        ent_all = None
+        if want_stats:
+            flat = np.concatenate(chosen)
+            img = np.repeat(np.arange(len(pending)), [len(c) for c in chosen])
+            if fused:
+                ent_all = acq.score_at_lowres(low, full_size, img, flat, "entropy", crop=(h, w), align_corners=align).cpu().numpy()
+            else:
+                dev = lg.device
+                picked = lg[torch.from_numpy(img).to(dev), :, torch.from_numpy(flat // w).to(dev), torch.from_numpy(flat % w).to(dev)]
+                ent_all = acq.score_map(picked.t().reshape(1, picked.shape[1], 1, -1).contiguous(), None, "entropy").reshape(-1).cpu().numpy()
+        off = 0
+        for j, it in enumerate(pending):
+            n_j = len(chosen[j])
+            self._emit(rd, it, chosen[j], ent_all[off:off + n_j] if want_stats else None)
+            off += n_j
+
+    def _score_mc_lowres(self, rd):
+        """MC-dropout from the classifier output, one image at a time: its passes in ONE forward that stops in front of the
+        upsample (the tensor the full-size route forwards: same dropout masks, same picks), one scoring launch (mean score
+        over the passes, exclusion and top-k in the kernel) and the entropy of the mean probability at the picked pixels
+        only - no full-size logits, no [C,H,W] probability map, no host entropy map.  (Images are not forwarded together:
+        the convolution planner picks its split-K form by the rows of the batch, so the logits of a joint forward differ
+        from the single ones in the last bits, and the dropout masks would change.)"""
+        T, align = self.mc_n_steps, rd.lowres_align
+        mc_topk = acq.mc_mean_topk_lowres if rd.mean_vote else acq.mc_vote_topk_lowres if rd.hard_vote else acq.mc_score_topk_lowres
+        for it in rd.pending:
+            h, w = it.size
+            excl_j = it.exclude | ~it.draws["cand"] if self.reverse_order else it.exclude
+            low, full_size = rd.model.forward_lowres(it.x.expand(T, -1, -1, -1).contiguous())
+            excl_t = self._excl_arg(excl_j)[None]
+            idx, _, _ = mc_topk(low, T, full_size, excl_t, self.query_strategy, self._k_launch(h, w), crop=(h, w), align_corners=align)
+            cand = self._drawn(it, self._spread(idx, excl_t, h, w)[0].cpu().numpy().astype(np.int64))[0]
+            ent = None
+            if not rd.human_labels and it.y is not None:
+                ent = acq.mc_score_at_lowres(low, T, full_size, np.zeros(len(cand), dtype=np.int32), cand, "entropy",
+                                             crop=(h, w), align_corners=align).cpu().numpy().astype(np.float64)
+            self._emit(rd, it, cand, ent)
+
+    def _score_per_image(self, rd):
+        """The full-size route, one image at a time: MC-dropout over full-size logits (chunked passes, the random strategy, models
+        without forward_lowres, wide heads), or a batch of mixed crops whose logits one forward made."""
+        pending, model = rd.pending, rd.model
+        is_random, is_bald = self.query_strategy == "random", self.query_strategy == "bald"
+        logits_b = None if self.use_mc_dropout else model(torch.cat([it.x for it in pending], dim=0))["pred"]
+
+        def ranked(uc_map, excl_t, h, w):
+            idx_t, _ = acq.topk_select(uc_map.reshape(1, h * w), self._k_launch(h, w), self._largest)
+            return self._spread(idx_t, excl_t, h, w)[0].cpu().numpy().astype(np.int64)
+
+        for j, it in enumerate(pending):
+            h, w = it.size
+            excl_j = it.exclude | ~it.draws["cand"] if self.reverse_order else it.exclude
+            if not self.use_mc_dropout:
+                logits = logits_b[j:j + 1, :, :h, :w]
+                if is_random:
+                    idx_sorted = self._random_topk(it.draws["rmap"][None], excl_j[None], self._k_launch(h, w))[0]
+                else:
+                    excl_t = self._excl_arg(excl_j)[None]
+                    idx_t, _, _ = acq.score_topk(logits, excl_t, self.query_strategy, self._k_launch(h, w))
+                    idx_sorted = self._spread(idx_t, excl_t, h, w)[0].cpu().numpy().astype(np.int64)
+                self._emit_with_stats(rd, it, self._drawn(it, idx_sorted)[0], lambda q: QueryStats._get_entropy_from_logits(q, logits))
+                continue
+            # mean uncertainty / mean probability over mc_n_steps stochastic passes: the passes differ only in their
+            # dropout masks (eval-mode BatchNorm is per sample), so they run as ONE forward over mc_n_steps copies of
+            # the image instead of mc_n_steps launch-bound forwards at batch 1 (`mc_chunk` copies at a time)
+            uc_map = torch.empty((h, w), dtype=torch.float32, device=self.device)
+            prob = torch.empty((1, self.n_classes, h, w), dtype=torch.float32, device=self.device)
+            votes = torch.empty((self.n_classes, h, w), dtype=torch.uint8, device=self.device) if rd.hard_vote else None
+            left, first = self.mc_n_steps, True
+            while left > 0:
+                t = min(left, self.mc_chunk)
+                logits = self._forward_logits(model, it.x.expand(t, -1, -1, -1).contiguous(), h, w)
+                # uc_map += score(softmax(logits)) / n ; prob += softmax(logits) / n   (query.py:181-187), one HIP pass
+                # hard vote: the mean probability for the statistics as before, the votes of the chunk beside it
+                # consensus: the mean probability alone; bald: the mean per-pass entropy beside it
+                soft_uc = None if is_random or rd.hard_vote or (rd.mean_vote and not is_bald) else uc_map
+                acq.mc_accumulate_(logits, prob[0], soft_uc, self.query_strategy if soft_uc is not None and not is_bald else "entropy",
+                                   1.0 / self.mc_n_steps, accumulate=not first)
+                if rd.hard_vote:
+                    acq.mc_vote_accumulate_(logits, votes, accumulate=not first)
+                left -= t
+                first = False
+            if is_random:                       # the drawn map is already the mean of the mc_n_steps host draws
+                idx_sorted = self._random_topk(it.draws["rmap"][None], excl_j[None], self._k_launch(h, w))[0]
+            elif rd.mean_vote:
+                excl_t = self._excl_arg(excl_j)[None]
+                uc_map = acq.mean_prob_score_map(prob, uc_map[None] if is_bald else None, excl_t, self.query_strategy)[0]
+                idx_sorted = ranked(uc_map, excl_t, h, w)
+            elif rd.hard_vote:
+                excl_t = self._excl_arg(excl_j)[None]
+                uc_map = acq.vote_score_map(votes, self.mc_n_steps, excl_t, self.query_strategy)[0]
+                idx_sorted = ranked(uc_map, excl_t, h, w)
+            else:
+                excl_t = torch.from_numpy(excl_j).to(self.device)
+                uc_map[excl_t] = 0.0 if self._largest else 1.0
+                idx_sorted = ranked(uc_map, excl_t[None], h, w)
+            self._emit_with_stats(rd, it, self._drawn(it, idx_sorted)[0], lambda q: QueryStats._get_entropy(q, prob))
+
+
     def __call__(self, nth_query, model, human_labels: bool = False):
         """One acquisition round (query.py:144-221).  With torch.distributed initialised the images are sharded
         `i -> rank i mod world`: every rank forwards / scores only its own images, ONE all_gather of the
@@ -466,281 +731,13 @@ class QuerySelector:
         if self.use_mc_dropout:
             model.turn_on_dropout()
 
-        self._check_balance(model)
-        self._check_diverse(model)
-        self._check_bald()
-        self._check_spread()
-        self._check_region(model)
+        self._check_options(model)
         print(f"Choosing pixels by {self.query_strategy}")
-        is_random = self.query_strategy == "random"
-        is_bald = self.query_strategy == "bald"
-        # the strategy on the mean probability of the passes (vote_type="consensus"), or their mutual information ("bald")
-        mean_vote = self.use_mc_dropout and not is_random and (is_bald or self.vote_type == "consensus")
-        records = []      # (image index, p_img, h, w, sorted flat indices int64, statistics contribution | None)
+        rd = self._plan_round(model, human_labels)
+        pending = rd.pending
         y = None
         n_seen = 0
-
-        pending = []      # _Item: x [1,3,H,W] on device, y numpy | None, exclude bool [h,w], p_img, (h, w), draws, index
-        inflight = []     # at most one launched-but-unfinished batch of the pipelined path
-        want_any_stats = not human_labels
-        # Low-resolution scoring, no reverse-order sampling: the GPU work of a batch is only ENQUEUED by flush(); its results
-        # come back through pinned buffers and are turned into masks / statistics after the next batch has been loaded and
-        # enqueued, so host and GPU overlap.
-        pipelined = (QUERY_PIPELINE and FUSED_LOWRES and not self.use_mc_dropout and hasattr(model, "forward_lowres")
-                     and not self.reverse_order and not is_random and torch.device(self.device).type == "cuda")
-        # MC-dropout (query.py:177-187) scored from the classifier output of all passes (pp_acq_lowres_mc_score_topk); chunked
-        # passes, the random strategy, models without forward_lowres and heads wider than the kernel keep the full-size route
-        mc_lowres = (FUSED_LOWRES and self.use_mc_dropout and hasattr(model, "forward_lowres") and not is_random
-                     and self.mc_n_steps <= self.mc_chunk
-                     and int(getattr(model, "n_classes", self.n_classes)) <= acq.MC_LOWRES_MAX_CLASSES)
-        # DeepLab: x4 align_corners=True (deeplab.py:55-56); FPNSeg: x2 align_corners=False (decoders.py:101)
-        lowres_align = bool(getattr(model, "LOWRES_ALIGN_CORNERS", True))
-        # args.py:34: the passes vote with their arg-max class and the strategy scores the vote shares (never a silent soft vote)
-        hard_vote = self.use_mc_dropout and self.vote_type == "hard" and not is_random
-        if hard_vote and not hasattr(model, "forward_lowres"):
-            # the vote is specified on pp_bilinear_fwd's logits; the picks of other models are pinned to the mean score
-            warnings.warn("vote_type='hard' needs a model with forward_lowres: this round uses the mean score (soft vote)", RuntimeWarning)
-            hard_vote = False
-        if hard_vote and not 1 <= self.mc_n_steps <= acq.MC_VOTE_MAX_PASSES:
-            raise ValueError(f"vote_type='hard' counts the votes in bytes: mc_n_steps = {self.mc_n_steps} is outside "
-                             f"[1, {acq.MC_VOTE_MAX_PASSES}]")
-        copy_stream = self.__dict__.get("_copy_stream")
-        if pipelined and copy_stream is None:
-            copy_stream = self.__dict__["_copy_stream"] = torch.cuda.Stream(device=self.device)
-
-        def emit(it, cand, cand_ent):
-            """cand: the chosen flat indices of image `it` (any order), cand_ent: their entropies in the same order | None."""
-            h, w = it.size
-            order = np.argsort(cand, kind="stable")
-            sel = np.asarray(cand, dtype=np.int64)[order]
-            contrib = None
-            if cand_ent is not None:
-                contrib = QueryStats.contribution(it.y, np.asarray(cand_ent)[order].tolist(), (sel // w, sel % w))
-            records.append((it.index, it.p_img, h, w, sel, contrib))
-
-        def choose(it, idx_sorted, ent_sorted=None):
-            """query.py:63-64 on the value-sorted top-k of one image -> (flat indices, their entropies | None)."""
-            pos = it.draws.get("pos")
-            if pos is not None:
-                return idx_sorted[pos], (ent_sorted[pos] if ent_sorted is not None else None)
-            return idx_sorted, ent_sorted
-
-        def finish(hd):
-            """Host half of a pipelined batch: wait for ITS read-back (not for whatever the GPU runs now)."""
-            items, idx_host, ent_host, ev = hd
-            ev.synchronize()
-            idx_h = idx_host.numpy().astype(np.int64)
-            ent_h = ent_host.numpy() if ent_host is not None else None
-            for j, it in enumerate(items):
-                emit(it, *choose(it, idx_h[j], ent_h[j] if ent_h is not None else None))
-
-        def launch_pipelined():
-            (h, w), = {it.size for it in pending}
-            main = torch.cuda.current_stream(self.device)
-            excl = np.ascontiguousarray(np.stack([it.exclude for it in pending]))
-            with torch.cuda.stream(copy_stream):               # a pageable upload on the main stream would block the host
-                excl_dev = torch.from_numpy(excl).view(torch.uint8).to(self.device)    # behind everything enqueued there
-            main.wait_stream(copy_stream)                      # images and exclusion masks of this batch have arrived
-            excl_dev.record_stream(main)
-            xs = torch.cat([it.x for it in pending], dim=0)
-            for it in pending:
-                it.x.record_stream(main)
-            low, full_size = model.forward_lowres(xs)
-            pred = None
-            if self._region_on:
-                idx, pred = self._region_topk(low, full_size, excl_dev, h, w, lowres_align)
-            else:
-                idx, _, _ = acq.score_topk_lowres(low, full_size, excl_dev, self.query_strategy, self._k_launch(h, w), crop=(h, w),
-                                                  align_corners=lowres_align)
-            idx = self._spread(idx, excl_dev, h, w)            # min_pixel_distance: [n,M] -> [n,n_pixels_by_us], on the device
-            idx = self._balance(idx, pred, low, full_size, excl_dev, h, w, lowres_align)      # class_balanced: likewise
-            idx = self._diverse(idx, low, full_size, excl_dev, h, w, lowres_align)             # diverse_picks: likewise
-            n, k = idx.shape
-            idx_host = torch.empty((n, k), dtype=torch.int32, pin_memory=True)
-            idx_host.copy_(idx, non_blocking=True)
-            ent_host = None
-            if want_any_stats and all(it.y is not None for it in pending):
-                img = torch.arange(n, device=idx.device, dtype=torch.int32).repeat_interleave(k)
-                ent = acq.score_at_lowres(low, full_size, img, idx.reshape(-1), "entropy", crop=(h, w), align_corners=lowres_align)
-                ent_host = torch.empty((n, k), dtype=torch.float32, pin_memory=True)
-                ent_host.copy_(ent.reshape(n, k), non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(main)
-            handle = (list(pending), idx_host, ent_host, ev)
-            pending.clear()
-            if inflight:
-                finish(inflight.pop())                         # the PREVIOUS batch, while the GPU works on this one
-            inflight.append(handle)
-
-        def flush():
-            if not pending:
-                return
-            if pipelined and len({it.size for it in pending}) == 1:
-                launch_pipelined()
-                return
-            if (self._region_on or self._balance_on or self._diverse_on) and len({it.size for it in pending}) > 1:
-                # equal padded shapes, different crops: one fused batch per size (the per-image routes below are neither region-scored
-                # nor class-balanced nor feature-diverse)
-                items = list(pending)
-                pending.clear()
-                for size in dict.fromkeys(it.size for it in items):
-                    pending.extend(it for it in items if it.size == size)
-                    flush()
-                return
-            if inflight:
-                finish(inflight.pop())
-            if pipelined:                                      # images were uploaded (and voc-padded) on copy_stream
-                main = torch.cuda.current_stream(self.device)
-                main.wait_stream(copy_stream)
-                for it in pending:
-                    it.x.record_stream(main)
-            xs = torch.cat([it.x for it in pending], dim=0)
-            logits_b = None
-            sizes = {it.size for it in pending}
-            # SURVEY.md §8f rank 1: DeepLab exposes its classifier output in front of the x4 upsample; the scoring
-            # kernel interpolates on the fly and the full-resolution logits are never written
-            fused = (FUSED_LOWRES and not self.use_mc_dropout and len(sizes) == 1 and hasattr(model, "forward_lowres"))
-            if fused:
-                low, full_size = model.forward_lowres(xs)
-            elif not self.use_mc_dropout:
-                logits_b = model(xs)["pred"]
-            if not self.use_mc_dropout and len(sizes) == 1:
-                # one scoring launch, one index read-back and one entropy read-back for the whole batch
-                (h, w), = sizes
-                excl = np.stack([it.exclude for it in pending])
-                if not fused:
-                    lg = logits_b[:, :, :h, :w]
-                if self.reverse_order:
-                    excl = excl | ~np.stack([it.draws["cand"] for it in pending])
-                if is_random:
-                    # the forward above only feeds the statistics (the reference runs it too, query.py:190)
-                    idx_h = self._random_topk(np.stack([it.draws["rmap"] for it in pending]), excl, self._k_launch(h, w))
-                elif fused:
-                    excl_t = self._excl_arg(excl)
-                    pred = None
-                    if self._region_on:
-                        idx, pred = self._region_topk(low, full_size, excl_t, h, w, lowres_align)
-                    else:
-                        idx, _, _ = acq.score_topk_lowres(low, full_size, excl_t, self.query_strategy,
-                                                          self._k_launch(h, w), crop=(h, w), align_corners=lowres_align)
-                    idx = self._balance(self._spread(idx, excl_t, h, w), pred, low, full_size, excl_t, h, w, lowres_align)
-                    idx = self._diverse(idx, low, full_size, excl_t, h, w, lowres_align)
-                    idx_h = idx.cpu().numpy().astype(np.int64)
-                else:
-                    excl_t = self._excl_arg(excl)
-                    idx, _, _ = acq.score_topk(lg, excl_t, self.query_strategy, self._k_launch(h, w))
-                    idx_h = self._spread(idx, excl_t, h, w).cpu().numpy().astype(np.int64)
-                chosen = [choose(it, idx_h[j])[0] for j, it in enumerate(pending)]
-                want_stats = (not human_labels) and all(it.y is not None for it in pending)
-                ent_all = None
-                if want_stats:
-                    flat = np.concatenate(chosen)
-                    img = np.repeat(np.arange(len(pending)), [len(c) for c in chosen])
-                    if fused:
-                        ent_all = acq.score_at_lowres(low, full_size, img, flat, "entropy", crop=(h, w), align_corners=lowres_align).cpu().numpy()
-                    else:
-                        dev = lg.device
-                        picked = lg[torch.from_numpy(img).to(dev), :, torch.from_numpy(flat // w).to(dev), torch.from_numpy(flat % w).to(dev)]
-                        ent_all = acq.score_map(picked.t().reshape(1, picked.shape[1], 1, -1).contiguous(), None, "entropy").reshape(-1).cpu().numpy()
-                off = 0
-                for j, it in enumerate(pending):
-                    n_j = len(chosen[j])
-                    emit(it, chosen[j], ent_all[off:off + n_j] if want_stats else None)
-                    off += n_j
-                pending.clear()
-                return
-            if mc_lowres:
-                # MC-dropout from the classifier output, one image at a time: its passes in ONE forward that stops in front of the
-                # upsample (the tensor the full-size route forwards: same dropout masks, same picks), one scoring launch (mean score
-                # over the passes, exclusion and top-k in the kernel) and the entropy of the mean probability at the picked pixels
-                # only - no full-size logits, no [C,H,W] probability map, no host entropy map.  (Images are not forwarded together:
-                # the convolution planner picks its split-K form by the rows of the batch, so the logits of a joint forward differ
-                # from the single ones in the last bits, and the dropout masks would change.)
-                T = self.mc_n_steps
-                for it in pending:
-                    h, w = it.size
-                    excl_j = it.exclude | ~it.draws["cand"] if self.reverse_order else it.exclude
-                    low, full_size = model.forward_lowres(it.x.expand(T, -1, -1, -1).contiguous())
-                    mc_topk = acq.mc_mean_topk_lowres if mean_vote else acq.mc_vote_topk_lowres if hard_vote else acq.mc_score_topk_lowres
-                    excl_t = self._excl_arg(excl_j)[None]
-                    idx, _, _ = mc_topk(low, T, full_size, excl_t,
-                                        self.query_strategy, self._k_launch(h, w), crop=(h, w), align_corners=lowres_align)
-                    cand = choose(it, self._spread(idx, excl_t, h, w)[0].cpu().numpy().astype(np.int64))[0]
-                    ent = None
-                    if not human_labels and it.y is not None:
-                        ent = acq.mc_score_at_lowres(low, T, full_size, np.zeros(len(cand), dtype=np.int32), cand, "entropy",
-                                                     crop=(h, w), align_corners=lowres_align).cpu().numpy().astype(np.float64)
-                    emit(it, cand, ent)
-                pending.clear()
-                return
-            for j, it in enumerate(pending):
-                h, w = it.size
-                excl_j = it.exclude | ~it.draws["cand"] if self.reverse_order else it.exclude
-                if self.use_mc_dropout:
-                    # mean uncertainty / mean probability over mc_n_steps stochastic passes: the passes differ only in their
-                    # dropout masks (eval-mode BatchNorm is per sample), so they run as ONE forward over mc_n_steps copies of
-                    # the image instead of mc_n_steps launch-bound forwards at batch 1 (`mc_chunk` copies at a time)
-                    uc_map = torch.empty((h, w), dtype=torch.float32, device=self.device)
-                    prob = torch.empty((1, self.n_classes, h, w), dtype=torch.float32, device=self.device)
-                    votes = torch.empty((self.n_classes, h, w), dtype=torch.uint8, device=self.device) if hard_vote else None
-                    left, first = self.mc_n_steps, True
-                    while left > 0:
-                        t = min(left, self.mc_chunk)
-                        logits = self._forward_logits(model, it.x.expand(t, -1, -1, -1).contiguous(), h, w)
-                        # uc_map += score(softmax(logits)) / n ; prob += softmax(logits) / n   (query.py:181-187), one HIP pass
-                        # hard vote: the mean probability for the statistics as before, the votes of the chunk beside it
-                        # consensus: the mean probability alone; bald: the mean per-pass entropy beside it
-                        soft_uc = None if is_random or hard_vote or (mean_vote and not is_bald) else uc_map
-                        acq.mc_accumulate_(logits, prob[0], soft_uc, self.query_strategy if soft_uc is not None and not is_bald else "entropy",
-                                           1.0 / self.mc_n_steps, accumulate=not first)
-                        if hard_vote:
-                            acq.mc_vote_accumulate_(logits, votes, accumulate=not first)
-                        left -= t
-                        first = False
-                    if is_random:                       # the drawn map is already the mean of the mc_n_steps host draws
-                        idx_sorted = self._random_topk(it.draws["rmap"][None], excl_j[None], self._k_launch(h, w))[0]
-                    elif mean_vote:
-                        excl_t = self._excl_arg(excl_j)[None]
-                        uc_map = acq.mean_prob_score_map(prob, uc_map[None] if is_bald else None, excl_t, self.query_strategy)[0]
-                        idx_t, _ = acq.topk_select(uc_map.reshape(1, h * w), self._k_launch(h, w), self._largest)
-                        idx_sorted = self._spread(idx_t, excl_t, h, w)[0].cpu().numpy().astype(np.int64)
-                    elif hard_vote:
-                        excl_t = self._excl_arg(excl_j)[None]
-                        uc_map = acq.vote_score_map(votes, self.mc_n_steps, excl_t, self.query_strategy)[0]
-                        idx_t, _ = acq.topk_select(uc_map.reshape(1, h * w), self._k_launch(h, w), self._largest)
-                        idx_sorted = self._spread(idx_t, excl_t, h, w)[0].cpu().numpy().astype(np.int64)
-                    else:
-                        excl_t = torch.from_numpy(excl_j).to(self.device)
-                        uc_map[excl_t] = 0.0 if self._largest else 1.0
-                        idx_t, _ = acq.topk_select(uc_map.reshape(1, h * w), self._k_launch(h, w), self._largest)
-                        idx_sorted = self._spread(idx_t, excl_t[None], h, w)[0].cpu().numpy().astype(np.int64)
-                    cand = choose(it, idx_sorted)[0]
-                    ent = None
-                    if not human_labels and it.y is not None:
-                        qmask = np.zeros(h * w, dtype=np.bool_)
-                        qmask[cand] = True
-                        ent_rowmajor = QueryStats._get_entropy(qmask.reshape(h, w), prob)     # row-major = ascending flat index
-                        ent = np.empty(len(cand), dtype=np.float64)
-                        ent[np.argsort(cand, kind="stable")] = ent_rowmajor
-                    emit(it, cand, ent)
-                else:
-                    logits = logits_b[j:j + 1, :, :h, :w]
-                    if is_random:
-                        idx_sorted = self._random_topk(it.draws["rmap"][None], excl_j[None], self._k_launch(h, w))[0]
-                    else:
-                        excl_t = self._excl_arg(excl_j)[None]
-                        idx_t, _, _ = acq.score_topk(logits, excl_t, self.query_strategy, self._k_launch(h, w))
-                        idx_sorted = self._spread(idx_t, excl_t, h, w)[0].cpu().numpy().astype(np.int64)
-                    cand = choose(it, idx_sorted)[0]
-                    ent = None
-                    if not human_labels and it.y is not None:
-                        qmask = np.zeros(h * w, dtype=np.bool_)
-                        qmask[cand] = True
-                        ent_rowmajor = QueryStats._get_entropy_from_logits(qmask.reshape(h, w), logits)
-                        ent = np.empty(len(cand), dtype=np.float64)
-                        ent[np.argsort(cand, kind="stable")] = ent_rowmajor
-                    emit(it, cand, ent)
-            pending.clear()
+        is_random, pipelined, copy_stream = self.query_strategy == "random", rd.pipelined, rd.copy_stream
 
         # Host side of the shard (SURVEY.md 8e): a rank's loader only reads and collates ITS images (index-level shard,
         # dist_utils.ShardedBatchSampler).  The host RNG streams must still advance through EVERY image in loader order (random
@@ -801,20 +798,20 @@ class QuerySelector:
                         x = F.pad(x, pad=(0, pad_w, 0, pad_h), mode='reflect')
 
                 if pending and (pending[0].x.shape != x.shape or len(pending) >= self.query_batch_size):
-                    flush()
+                    self._flush(rd)
                 pending.append(_Item(x, y_np, exclude, dict_data["p_img"][0], (h, w), draws, batch_ind))
                 if len(pending) >= self.query_batch_size:
-                    flush()
-            flush()
-            if inflight:
-                finish(inflight.pop())
+                    self._flush(rd)
+            self._flush(rd)
+            if rd.inflight:
+                self._finish_pipelined(rd, rd.inflight.pop())
         if sharded is not None:
             n_seen = len(dataset)
             if needs_rng:
                 for j in range(next_draw, n_seen):             # trailing images of other ranks: leave the streams where a
                     self._draw(*sizes[j])                      # single-rank round would leave them
 
-        records = dist_utils.gather_records(records, world, group)     # ~100 B per image, the only exchange of the round; loader order
+        records = dist_utils.gather_records(rd.records, world, group)    # ~100 B per image, the only exchange of the round; loader order
         assert len(records) == n_seen and n_seen > 0, f"no queries are chosen!" if n_seen == 0 else (len(records), n_seen)
         dict_queries: dict = dict()
         n_pixels = 0
@@ -837,6 +834,18 @@ class QuerySelector:
             if world > 1:
                 torch.distributed.barrier(group=group)
         return dict_queries
+
+
+class _Round:
+    """One acquisition round: what QuerySelector._plan_round decides once, and the lists its routes fill."""
+    __slots__ = ("model", "human_labels", "pipelined", "mc_lowres", "hard_vote", "mean_vote", "lowres_align", "copy_stream",
+                 "records", "pending", "inflight")
+
+    def __init__(self, model, human_labels):
+        self.model, self.human_labels = model, human_labels
+        self.records = []     # (image index, p_img, h, w, sorted flat indices int64, statistics contribution | None)
+        self.pending = []     # _Item: x [1,3,H,W] on device, y numpy | None, exclude bool [h,w], p_img, (h, w), draws, index
+        self.inflight = []    # at most one launched-but-unfinished batch of the pipelined route
 
 
 class _Item:

@@ -1,4 +1,4 @@
-"""GPU tests of pp_class_balance_select (csrc/acq.hip, class_balance_kernel) against the plain-Python oracle (tests/balance_oracle.py):
+"""GPU tests of pp_class_balance_select (csrc/acq_select.hip, class_balance_kernel) against the plain-Python oracle (tests/balance_oracle.py):
 idx, pos and n must be equal, integer for integer.  The shapes sit where the kernel can go wrong: the edges of its 64-candidate chunks and
 of the 1024-candidate strides of its counting walk, the pools of the 64 x 96 golden size (307) and of 256 x 512 (6553), one class and 256 of
 them, a class that only appears at the end of the list, the fill phase, candidates outside the image, several images per launch and a

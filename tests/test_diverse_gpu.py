@@ -1,4 +1,4 @@
-"""GPU tests of pp_diverse_select (csrc/acq.hip, diverse_kernel) against the numpy oracle (tests/diverse_oracle.py): idx, pos, dist and n
+"""GPU tests of pp_diverse_select (csrc/acq_select.hip, diverse_kernel) against the numpy oracle (tests/diverse_oracle.py): idx, pos, dist and n
 must be equal, integer for integer.  The shapes sit where the kernel can go wrong: one candidate, the edges of a wave and of the
 1024-thread block, the pools of the 64 x 96 golden size (307) and of 256 x 512 (6553), the switch between the resident and the streaming
 form, feature rows of one byte, of whole and of ragged dwords and of the full 256 bytes, padded rows, the fill phase, candidates outside

@@ -1,4 +1,4 @@
-"""GPU tests of pp_acq_region_score_map (csrc/acq.hip, region_score_kernel) against the numpy oracle (tests/region_oracle.py).
+"""GPU tests of pp_acq_region_score_map (csrc/acq_select.hip, region_score_kernel) against the numpy oracle (tests/region_oracle.py).
 
 The impurity is an integer computation: mode 1 must be BIT-equal.  The window uncertainty is an fp32 sum of K = (2r+1)^2 non-negative
 terms, one division and one int -> float conversion, each at most 2^-24 relative, doubled: (K+2) 2^-23 relative to float64; the

@@ -1,4 +1,4 @@
-"""GPU tests of pp_spread_select (csrc/acq.hip, spread_select_kernel) against the numpy oracle (tests/spread_oracle.py): idx, pos and n
+"""GPU tests of pp_spread_select (csrc/acq_select.hip, spread_select_kernel) against the numpy oracle (tests/spread_oracle.py): idx, pos and n
 must be bit-equal.  The shapes sit where the kernel can go wrong: the edges of its 64-candidate chunks, the rank order inside one chunk,
 a pick of an earlier chunk that blocks a later one, the fill phase, masks, several images per launch and coordinates whose squared
 difference leaves 32 bits."""

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel register / scratch / occupancy table of one HIP source (hipcc -Rpass-analysis=kernel-resource-usage), CPU only.
 
-    python tools/kernel_resources.py pixelpick_amd/csrc/acq.hip [name-filter]
+    python tools/kernel_resources.py pixelpick_amd/csrc/acq_select.hip [name-filter]
 """
 import os
 import re

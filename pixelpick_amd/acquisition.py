@@ -2,7 +2,8 @@
 
 Everything here only marshals torch device tensors (pointers, strides, current stream) into
 include/pixelpick_hip.h calls; all arithmetic runs in the hand-written HIP kernels (csrc/acq.hip: the
-scorers and the ranking; csrc/acq_select.hip: the selectors that run after it).
+full-size scorers; csrc/acq_lowres.hip: the scorers on the classifier-resolution logits; csrc/acq_mc.hip: the MC-dropout families;
+csrc/acq_topk.hip: the ranking of a score map; csrc/acq_select.hip: the selectors that run after it).
 """
 from typing import Optional, Tuple
 

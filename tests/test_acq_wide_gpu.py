@@ -1,4 +1,4 @@
-"""GPU parity tests of the STREAMED scorers (csrc/acq.hip acq_stream_kernel / acq_lowres_stream_kernel): class counts beyond the
+"""GPU parity tests of the STREAMED scorers (csrc/acq.hip acq_stream_kernel / csrc/acq_lowres.hip acq_lowres_stream_kernel): class counts beyond the
 register-resident kernels' 64.  The reference softmaxes whatever width the model emits (query.py:190) and its samplers reduce over
 dim 1 of any size (query.py:229-239), so no class count may be rejected.
   * forced onto C <= 64 inputs (pp_debug_set_acq_tuning(10, 0)) the streamed kernels are BIT-EQUAL to the register kernels:

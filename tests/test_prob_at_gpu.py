@@ -1,4 +1,4 @@
-"""GPU tests of pp_acq_lowres_prob_at_u8 (csrc/acq.hip, prob_at_kernel / prob_at_stream_kernel) against the oracle's codes
+"""GPU tests of pp_acq_lowres_prob_at_u8 (csrc/acq_lowres.hip, prob_at_kernel / prob_at_stream_kernel) against the oracle's codes
 (tests/diverse_oracle.py: float64 softmax of the fp32-interpolated logits, min(255, rint(255 p))).
 
 A code can only differ from the oracle's when 255 p lies within the fp32 error of a half-integer: no code may differ by more than 1, and

@@ -2,6 +2,9 @@
 """Per-kernel register / scratch / occupancy table of one HIP source (hipcc -Rpass-analysis=kernel-resource-usage), CPU only.
 
     python tools/kernel_resources.py pixelpick_amd/csrc/acq_select.hip [name-filter]
+
+The acquisition kernels are one source per stage: acq.hip (full-size scorers, list select), acq_topk.hip (selection on a score map),
+acq_lowres.hip (scorers on the classifier-resolution logits, prob_at), acq_mc.hip (MC-dropout families), acq_select.hip.
 """
 import os
 import re

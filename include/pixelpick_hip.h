@@ -774,6 +774,34 @@ int pp_sparse_ce_lowres_fwd_bwd(const float* low, int64_t ldx, int B, int C, int
                                 const int64_t* target, int ignore_index, float* loss, float* count, const float* grad_out,
                                 float* dlow, int64_t lddx, void* workspace, size_t ws_bytes, pp_stream_t stream);
 
+/* The two entries above with the arguments a user of model.py:116's call reaches for first when classes are imbalanced:
+ *   F.cross_entropy(x, y, weight=class_weight, ignore_index=ignore_index, reduction="mean", label_smoothing=eps)
+ * Per labelled pixel i with target y_i:  lp_c = x_c - m - log S,  m = max_c x_c,  S = sum_c expf(x_c - m)  (classes ascending, one
+ * running sum, as in the un-weighted kernels);  w = class_weight, NULL = all ones (so smoothing alone works):
+ *   A    = sum_i w[y_i] * (-lp_{y_i})                   Bsm = sum_i sum_c w[c] * (-lp_c)   (only when eps > 0)
+ *   Wsum = sum_i w[y_i]                                 Wall = sum_c w[c]                  (fp32, classes ascending)
+ *   *loss = (1 - eps) * A / Wsum + (eps / C) * Bsm / Wsum,    *wsum = Wsum   (the place of the un-weighted entries' *count)
+ *   d loss / d x_c at pixel i = [ (1 - eps) * w[y_i] * (p_c - [c == y_i]) + (eps / C) * (p_c * Wall - w[c]) ] / Wsum
+ * dlogits / dlow (NULL: loss only) = grad_out (NULL: 1) times that gradient, chained through the interpolation for the
+ * low-resolution entry; fully written, zero wherever no pixel is labelled (pp_row_flags and the sparse backward still apply).
+ * A pixel is labelled iff target != ignore_index AND 0 <= target < C: any other target adds to no sum and no gradient, and
+ * class_weight (f32 [C], device) is never indexed out of range.  Wsum == 0 (no labelled pixel, or all of them in classes of
+ * weight 0) gives a NaN loss, as torch does.  Layouts, lddx, the workspace (pp_sparse_ce_(lowres_)workspace_bytes()), the
+ * double-precision fixed-order finalize, the class-count dispatch (registers up to 64 classes, streamed in chunks of 64 beyond) and
+ * the bitwise reproducibility are the un-weighted entries'; with weights all 1.0 and eps 0 the outputs equal theirs bit for bit
+ * (up to the sign of a zero).
+ * Errors: PP_ERR_BAD_ARG  a NULL among logits / low, target, loss, wsum; a shape below 1, ldx < C, lddx < C with dlow;
+ *                         label_smoothing outside [0, 1] or NaN - all before anything is enqueued;
+ *         PP_ERR_WORKSPACE   workspace NULL or smaller than the query's answer;
+ *         PP_ERR_UNSUPPORTED more than 65535 chunks of 64 classes;  PP_ERR_LAUNCH a failed launch. */
+int pp_sparse_ce_weighted_fwd_bwd(const float* logits, int B, int C, int64_t HW, int64_t sB, int64_t sC, const int64_t* target,
+                                  int ignore_index, const float* class_weight, float label_smoothing, float* loss, float* wsum,
+                                  const float* grad_out, float* dlogits, void* workspace, size_t ws_bytes, pp_stream_t stream);
+int pp_sparse_ce_lowres_weighted_fwd_bwd(const float* low, int64_t ldx, int B, int C, int h, int w, int H, int W, int align_corners,
+                                         const int64_t* target, int ignore_index, const float* class_weight, float label_smoothing,
+                                         float* loss, float* wsum, const float* grad_out, float* dlow, int64_t lddx, void* workspace,
+                                         size_t ws_bytes, pp_stream_t stream);
+
 /* Step metrics on the device (model.py:124-125,194-196 + utils/metrics.py:168-177): hist[t*C + argmax_c logits] += 1
  * for every pixel whose target t is in [0, C) (ignore_index >= C is skipped like RunningScore._fast_hist).  hist is
  * an int64 [C,C] accumulator the caller zeroes / reads (C*C*8 bytes D2H instead of two full maps).

@@ -147,6 +147,8 @@ SIGNATURES = {
     "pp_sparse_ce_fwd_bwd": (_int, [_p, _int, _int, _i64, _i64, _i64, _p, _int, _p, _p, _p, _p, _p, _sz, _p]),
     "pp_sparse_ce_lowres_workspace_bytes": (_sz, []),
     "pp_sparse_ce_lowres_fwd_bwd": (_int, [_p, _i64] + [_int] * 7 + [_p, _int, _p, _p, _p, _p, _i64, _p, _sz, _p]),
+    "pp_sparse_ce_weighted_fwd_bwd": (_int, [_p, _int, _int, _i64, _i64, _i64, _p, _int, _p, _f, _p, _p, _p, _p, _p, _sz, _p]),
+    "pp_sparse_ce_lowres_weighted_fwd_bwd": (_int, [_p, _i64] + [_int] * 7 + [_p, _int, _p, _f, _p, _p, _p, _p, _i64, _p, _sz, _p]),
     "pp_confusion_matrix_update": (_int, [_p, _int, _int, _i64, _i64, _i64, _p, _p, _p]),
     "pp_predict_lowres": (_int, [_p] + [_i64] * 7 + [_int, _i64, _i64, _p, _int, _p, _p, _p]),
     "pp_confusion_matrix_from_labels": (_int, [_p, _p, _int, _i64, _int, _p, _p]),

@@ -1906,24 +1906,64 @@ __global__ __launch_bounds__(kT) void dropout_kernel(const float* x, int64_t ldx
 // cross entropy with ignore_index on NCHW logits (model.py:116): loss = mean over labelled pixels of
 // (logsumexp - x[target]); dlogits = (softmax - onehot)/N at labelled pixels, 0 elsewhere.
 // ================================================================================================
+// The weighted forms (F.cross_entropy's weight= and label_smoothing=) are the SAME kernel sources with WT = true: every loss
+// kernel below takes a trailing CeW<WT>, empty for the un-weighted instantiations (the ones the un-weighted entries launch, with
+// their code as it was).  Per labelled pixel i (WT: target != ignore_index AND 0 <= target < C, so cw is never indexed out of range;
+// un-weighted: target != ignore_index), lse = m + log S:
+//   term_i = (1-eps) * (w[y_i] * (lse - x_{y_i}))  +  (eps/C) * sum_c w[c] * (lse - x_c)       second addend only when eps > 0
+//   loss   = sum_i term_i / Wsum,   Wsum = sum_i w[y_i]                                          (the same two block partials)
+//   d loss / d x_c = [ ((1-eps) * w[y_i]) * (p_c - [c == y_i])  +  (eps/C) * (p_c * Wall - w[c]) ] / Wsum,   Wall = sum_c w[c]
+// Classes ascending, one running sum (Wall too: the register and the streamed form agree).  With w = 1, eps = 0 every extra
+// operation is a multiplication by an exact 1, so the bits are the un-weighted kernels'.  The weights are read at wave-uniform
+// addresses (the class loops) except w[y_i], one gather per labelled pixel.
+template <bool WT>
+struct CeW {};
+template <>
+struct CeW<true> {
+    const float* cw;   // [C] or nullptr = all ones
+    float om;          // 1 - eps
+    float sc;          // eps / C; 0 = no smoothing term
+    __device__ __forceinline__ float w(int64_t c) const { return cw ? cw[c] : 1.0f; }
+    __device__ __forceinline__ float wall(int C) const
+    {
+        float s = 0.0f;
+        for (int c = 0; c < C; ++c) s += w(c);
+        return s;
+    }
+};
+
+template <bool WT = false>
 __global__ __launch_bounds__(kT) void ce_partial_kernel(const float* logits, const int64_t* target, int B, int C, int64_t HW,
-                                                       int64_t sB, int64_t sC, int ignore_index, float* part /*[nblk][2]*/)
+                                                       int64_t sB, int64_t sC, int ignore_index, float* part /*[nblk][2]*/,
+                                                       CeW<WT> cw = {})
 {
     __shared__ float sh[2][kT];
     float ls = 0.0f, cnt = 0.0f;
     const int64_t total = (int64_t)B * HW;
     for (int64_t e = (int64_t)blockIdx.x * kT + threadIdx.x; e < total; e += (int64_t)gridDim.x * kT) {
         const int64_t tg = target[e];
-        if (tg == ignore_index) continue;
+        if (tg == ignore_index || (WT && (tg < 0 || tg >= C))) continue;
         const int64_t b = e / HW, pix = e - b * HW;
         const float* px = logits + b * sB + pix;
         float m = px[0];
         for (int c = 1; c < C; ++c) m = fmaxf(m, px[c * sC]);
         float S = 0.0f;
         for (int c = 0; c < C; ++c) S += expf(px[c * sC] - m);
-        const float xt = (tg >= 0 && tg < C) ? px[tg * sC] : 0.0f;
-        ls += (m + logf(S)) - xt;
-        cnt += 1.0f;
+        if constexpr (WT) {
+            const float lse = m + logf(S), wt = cw.w(tg);
+            float term = cw.om * (wt * (lse - px[tg * sC]));
+            if (cw.sc > 0.0f) {
+                float bs = 0.0f;
+                for (int c = 0; c < C; ++c) bs += cw.w(c) * (lse - px[c * sC]);
+                term += cw.sc * bs;
+            }
+            ls += term;
+            cnt += wt;
+        } else {
+            const float xt = (tg >= 0 && tg < C) ? px[tg * sC] : 0.0f;
+            ls += (m + logf(S)) - xt;
+            cnt += 1.0f;
+        }
     }
     sh[0][threadIdx.x] = ls;
     sh[1][threadIdx.x] = cnt;
@@ -1939,17 +1979,20 @@ __global__ __launch_bounds__(kT) void ce_partial_kernel(const float* logits, con
 }
 
 // dlogits (NCHW contiguous) = grad_scale * (softmax - onehot) / N at labelled pixels, 0 elsewhere
+template <bool WT = false>
 __global__ __launch_bounds__(kT) void ce_bwd_kernel(const float* logits, const int64_t* target, int B, int C, int64_t HW,
                                                    int64_t sB, int64_t sC, int ignore_index, const float* count,
-                                                   const float* grad_out, float* dlogits)
+                                                   const float* grad_out, float* dlogits, CeW<WT> cw = {})
 {
     const int64_t total = (int64_t)B * HW;
     const float gs = (grad_out ? *grad_out : 1.0f) / *count;
+    float wall = 0.0f;
+    bool have_wall = false;   // Wall is summed at the thread's first labelled pixel: most threads never meet one
     for (int64_t e = (int64_t)blockIdx.x * kT + threadIdx.x; e < total; e += (int64_t)gridDim.x * kT) {
         const int64_t tg = target[e];
         const int64_t b = e / HW, pix = e - b * HW;
         float* dst = dlogits + (b * C) * HW + pix;
-        if (tg == ignore_index) {
+        if (tg == ignore_index || (WT && (tg < 0 || tg >= C))) {
             for (int c = 0; c < C; ++c) dst[c * HW] = 0.0f;
             continue;
         }
@@ -1959,9 +2002,20 @@ __global__ __launch_bounds__(kT) void ce_bwd_kernel(const float* logits, const i
         float S = 0.0f;
         for (int c = 0; c < C; ++c) S += expf(px[c * sC] - m);
         const float inv = 1.0f / S;
+        float a = 1.0f;
+        if constexpr (WT) {
+            a = cw.om * cw.w(tg);
+            if (cw.sc > 0.0f && !have_wall) { wall = cw.wall(C); have_wall = true; }
+        }
         for (int c = 0; c < C; ++c) {
             const float pr = expf(px[c * sC] - m) * inv;
-            dst[c * HW] = gs * (pr - (c == tg ? 1.0f : 0.0f));
+            if constexpr (WT) {
+                float g = a * (pr - (c == tg ? 1.0f : 0.0f));   // a == 1 leaves the un-weighted kernel's bits
+                if (cw.sc > 0.0f) g += cw.sc * (pr * wall - cw.w(c));
+                dst[c * HW] = gs * g;
+            } else {
+                dst[c * HW] = gs * (pr - (c == tg ? 1.0f : 0.0f));
+            }
         }
     }
 }
@@ -1976,17 +2030,17 @@ __global__ __launch_bounds__(kT) void ce_bwd_kernel(const float* logits, const i
 // vector only where a label is, the backward GATHERS per low-resolution pixel from the labelled pixels in its
 // footprint (fixed order, no atomics: bitwise reproducible).
 // ================================================================================================
-template <int CMAX, bool EXACT>
+template <int CMAX, bool EXACT, bool WT = false>
 __global__ __launch_bounds__(kT) void ce_lowres_partial_kernel(const float* low, int64_t ldx, int B, int C, int h, int w, int H,
                                                               int W, float sh, float sw, int align, const int64_t* target,
-                                                              int ignore_index, float* part /*[nblk][2]*/)
+                                                              int ignore_index, float* part /*[nblk][2]*/, CeW<WT> cw = {})
 {
     __shared__ float shm[2][kT];
     float ls = 0.0f, cnt = 0.0f;
     const int64_t HW = (int64_t)H * W, total = (int64_t)B * HW;
     for (int64_t e = (int64_t)blockIdx.x * kT + threadIdx.x; e < total; e += (int64_t)gridDim.x * kT) {
         const int64_t tg = target[e];
-        if (tg == ignore_index) continue;
+        if (tg == ignore_index || (WT && (tg < 0 || tg >= C))) continue;
         const int64_t b = e / HW, pix = e - b * HW;
         const int Y = (int)(pix / W), X = (int)(pix - (int64_t)Y * W);
         float x[CMAX];
@@ -2002,8 +2056,22 @@ __global__ __launch_bounds__(kT) void ce_lowres_partial_kernel(const float* low,
                 S += expf(x[c] - m);
                 xt = (c == tg) ? x[c] : xt;
             }
-        ls += (m + logf(S)) - xt;
-        cnt += 1.0f;
+        if constexpr (WT) {
+            const float lse = m + logf(S), wt = cw.w(tg);
+            float term = cw.om * (wt * (lse - xt));
+            if (cw.sc > 0.0f) {
+                float bs = 0.0f;
+#pragma unroll
+                for (int c = 0; c < CMAX; ++c)
+                    if (EXACT || c < C) bs += cw.w(c) * (lse - x[c]);
+                term += cw.sc * bs;
+            }
+            ls += term;
+            cnt += wt;
+        } else {
+            ls += (m + logf(S)) - xt;
+            cnt += 1.0f;
+        }
     }
     shm[0][threadIdx.x] = ls;
     shm[1][threadIdx.x] = cnt;
@@ -2019,6 +2087,9 @@ __global__ __launch_bounds__(kT) void ce_lowres_partial_kernel(const float* low,
 }
 
 // one 64-lane wave, fixed order: lane l adds part[l], part[l+64], ... in double, then a fixed shuffle tree
+// WT: with a smoothing term the numerator is positive even when every labelled pixel sits in a class of weight 0; torch adds
+// (1-eps) * 0/0 to it, so Wsum == 0 is a NaN loss there too
+template <bool WT = false>
 __global__ __launch_bounds__(64) void ce_finalize_wave_kernel(const float* part, int nblk, float* loss, float* count)
 {
     double s = 0.0, n = 0.0;
@@ -2029,17 +2100,18 @@ __global__ __launch_bounds__(64) void ce_finalize_wave_kernel(const float* part,
     }
     if (threadIdx.x == 0) {
         *count = (float)n;
-        *loss = (float)(s / n);   // 0/0 = NaN when no pixel is labelled, like F.cross_entropy
+        if constexpr (WT) *loss = n == 0.0 ? __builtin_nanf("") : (float)(s / n);
+        else *loss = (float)(s / n);   // 0/0 = NaN when no pixel is labelled, like F.cross_entropy
     }
 }
 
 // One thread per low-resolution pixel: walk the output pixels that interpolate from it, and for the (rare) labelled
 // ones add  weight * (softmax - onehot).  dlow [B,h,w,lddx] is fully written (zeros included).
-template <int CMAX, bool EXACT>
+template <int CMAX, bool EXACT, bool WT = false>
 __global__ __launch_bounds__(kT) void ce_lowres_bwd_kernel(const float* low, int64_t ldx, int B, int C, int h, int w, int H,
                                                           int W, float sh, float sw, int align, const int64_t* target,
                                                           int ignore_index, const float* count, const float* grad_out,
-                                                          float* dlow, int64_t lddx)
+                                                          float* dlow, int64_t lddx, CeW<WT> cw = {})
 {
     const int64_t total = (int64_t)B * h * w;
     const int64_t e = (int64_t)blockIdx.x * kT + threadIdx.x;
@@ -2049,6 +2121,8 @@ __global__ __launch_bounds__(kT) void ce_lowres_bwd_kernel(const float* low, int
     const int r0 = (int)(t % h);
     const int b = (int)(t / h);
     const float gs = (grad_out ? *grad_out : 1.0f) / *count;
+    float wall = 0.0f;
+    bool have_wall = false;   // Wall is summed at the thread's first labelled pixel: most threads never meet one
     float acc[CMAX];
 #pragma unroll
     for (int c = 0; c < CMAX; ++c) acc[c] = 0.0f;
@@ -2064,7 +2138,7 @@ __global__ __launch_bounds__(kT) void ce_lowres_bwd_kernel(const float* low, int
         const int64_t* trow = tb + (int64_t)Y * W;
         for (int X = xlo; X <= xhi; ++X) {
             const int64_t tg = trow[X];
-            if (tg == ignore_index) continue;
+            if (tg == ignore_index || (WT && (tg < 0 || tg >= C))) continue;
             const Lerp lw = lerp_src(X, w, sw, align);
             if (lw.i0 != c0 && lw.i1 != c0) continue;
             const float ww = (lw.i0 == c0 ? lw.l0 : 0.0f) + (lw.i1 == c0 ? lw.l1 : 0.0f);
@@ -2082,9 +2156,21 @@ __global__ __launch_bounds__(kT) void ce_lowres_bwd_kernel(const float* low, int
                     S += x[c];
                 }
             const float inv = 1.0f / S, wgt = wh * ww;
+            if constexpr (WT) {
+                const float a = cw.om * cw.w(tg);
+                if (cw.sc > 0.0f && !have_wall) { wall = cw.wall(C); have_wall = true; }
 #pragma unroll
-            for (int c = 0; c < CMAX; ++c)
-                if (EXACT || c < C) acc[c] = fmaf(wgt, gs * (x[c] * inv - (c == tg ? 1.0f : 0.0f)), acc[c]);
+                for (int c = 0; c < CMAX; ++c)
+                    if (EXACT || c < C) {
+                        float g = a * (x[c] * inv - (c == tg ? 1.0f : 0.0f));
+                        if (cw.sc > 0.0f) g += cw.sc * ((x[c] * inv) * wall - cw.w(c));
+                        acc[c] = fmaf(wgt, gs * g, acc[c]);
+                    }
+            } else {
+#pragma unroll
+                for (int c = 0; c < CMAX; ++c)
+                    if (EXACT || c < C) acc[c] = fmaf(wgt, gs * (x[c] * inv - (c == tg ? 1.0f : 0.0f)), acc[c]);
+            }
         }
     }
     float* dst = dlow + e * lddx;
@@ -2115,23 +2201,37 @@ __device__ __forceinline__ void ce_stream_stats(const LowresTaps<>& t, int C, in
     }
 }
 
+template <bool WT = false>
 __global__ __launch_bounds__(kT) void ce_lowres_stream_partial_kernel(const float* low, int64_t ldx, int B, int C, int h, int w, int H,
                                                                      int W, float sh, float sw, int align, const int64_t* target,
-                                                                     int ignore_index, float* part /*[nblk][2]*/)
+                                                                     int ignore_index, float* part /*[nblk][2]*/, CeW<WT> cw = {})
 {
     __shared__ float shm[2][kT];
     float ls = 0.0f, cnt = 0.0f;
     const int64_t HW = (int64_t)H * W, total = (int64_t)B * HW;
     for (int64_t e = (int64_t)blockIdx.x * kT + threadIdx.x; e < total; e += (int64_t)gridDim.x * kT) {
         const int64_t tg = target[e];
-        if (tg == ignore_index) continue;
+        if (tg == ignore_index || (WT && (tg < 0 || tg >= C))) continue;
         const int64_t b = e / HW, pix = e - b * HW;
         const int Y = (int)(pix / W), X = (int)(pix - (int64_t)Y * W);
         const auto t = lowres_taps(low + b * h * w * ldx, ldx, w, lerp_src(Y, h, sh, align), lerp_src(X, w, sw, align));
         float m, S, xt;
         ce_stream_stats(t, C, tg, m, S, xt);
-        ls += (m + logf(S)) - xt;
-        cnt += 1.0f;
+        if constexpr (WT) {
+            const float lse = m + logf(S), wt = cw.w(tg);
+            float term = cw.om * (wt * (lse - xt));
+            if (cw.sc > 0.0f) {   // pass 3 over the same 4*C floats: the smoothing term's weighted sum of -log p_c
+                float bs = 0.0f;
+#pragma unroll 8
+                for (int c = 0; c < C; ++c) bs += cw.w(c) * (lse - t.at(c));
+                term += cw.sc * bs;
+            }
+            ls += term;
+            cnt += wt;
+        } else {
+            ls += (m + logf(S)) - xt;
+            cnt += 1.0f;
+        }
     }
     shm[0][threadIdx.x] = ls;
     shm[1][threadIdx.x] = cnt;
@@ -2151,10 +2251,11 @@ __global__ __launch_bounds__(kT) void ce_lowres_stream_partial_kernel(const floa
 // output pixel it recomputes (max, 1/sum) over ALL classes - labelled pixels are rare, and a stash would cost a workspace sized
 // by the label map - and adds its chunk's  weight * (softmax - onehot).  Fixed order, no atomics; dlow fully written.
 constexpr int kCeChunk = 64;
+template <bool WT = false>
 __global__ __launch_bounds__(kT) void ce_lowres_stream_bwd_kernel(const float* low, int64_t ldx, int B, int C, int h, int w, int H,
                                                                  int W, float sh, float sw, int align, const int64_t* target,
                                                                  int ignore_index, const float* count, const float* grad_out,
-                                                                 float* dlow, int64_t lddx)
+                                                                 float* dlow, int64_t lddx, CeW<WT> cw = {})
 {
     const int64_t total = (int64_t)B * h * w;
     const int64_t e = (int64_t)blockIdx.x * kT + threadIdx.x;
@@ -2166,6 +2267,8 @@ __global__ __launch_bounds__(kT) void ce_lowres_stream_bwd_kernel(const float* l
     const int r0 = (int)(t % h);
     const int b = (int)(t / h);
     const float gs = (grad_out ? *grad_out : 1.0f) / *count;
+    float wall = 0.0f;
+    bool have_wall = false;   // Wall is summed at the thread's first labelled pixel: most threads never meet one
     float acc[kCeChunk];
 #pragma unroll
     for (int j = 0; j < kCeChunk; ++j) acc[j] = 0.0f;
@@ -2181,7 +2284,7 @@ __global__ __launch_bounds__(kT) void ce_lowres_stream_bwd_kernel(const float* l
         const int64_t* trow = tb + (int64_t)Y * W;
         for (int X = xlo; X <= xhi; ++X) {
             const int64_t tg = trow[X];
-            if (tg == ignore_index) continue;
+            if (tg == ignore_index || (WT && (tg < 0 || tg >= C))) continue;
             const Lerp lw = lerp_src(X, w, sw, align);
             if (lw.i0 != c0 && lw.i1 != c0) continue;
             const float ww = (lw.i0 == c0 ? lw.l0 : 0.0f) + (lw.i1 == c0 ? lw.l1 : 0.0f);
@@ -2190,9 +2293,22 @@ __global__ __launch_bounds__(kT) void ce_lowres_stream_bwd_kernel(const float* l
             ce_stream_stats(tp, C, tg, m, S, xt);
             const float inv = 1.0f / S, wgt = wh * ww;
             const int64_t jt = tg - cb;                    // the target's place in this chunk (outside [0, nc): not in it)
+            if constexpr (WT) {
+                const float a = cw.om * cw.w(tg);
+                if (cw.sc > 0.0f && !have_wall) { wall = cw.wall(C); have_wall = true; }
 #pragma unroll
-            for (int j = 0; j < kCeChunk; ++j)
-                if (j < nc) acc[j] = fmaf(wgt, gs * (expf(tp.at(cb + j) - m) * inv - ((int64_t)j == jt ? 1.0f : 0.0f)), acc[j]);
+                for (int j = 0; j < kCeChunk; ++j)
+                    if (j < nc) {
+                        const float ex = expf(tp.at(cb + j) - m);
+                        float g = a * (ex * inv - ((int64_t)j == jt ? 1.0f : 0.0f));
+                        if (cw.sc > 0.0f) g += cw.sc * ((ex * inv) * wall - cw.w(cb + j));
+                        acc[j] = fmaf(wgt, gs * g, acc[j]);
+                    }
+            } else {
+#pragma unroll
+                for (int j = 0; j < kCeChunk; ++j)
+                    if (j < nc) acc[j] = fmaf(wgt, gs * (expf(tp.at(cb + j) - m) * inv - ((int64_t)j == jt ? 1.0f : 0.0f)), acc[j]);
+            }
         }
     }
     float* dst = dlow + e * lddx + cb;
@@ -2320,6 +2436,85 @@ static int need_c4(int C, const char* what)
 {
     if (C < 4 || C % 4 != 0) return fail(PP_ERR_UNSUPPORTED, "%s: C=%d must be a positive multiple of 4", what, C);
     return PP_OK;
+}
+
+// ---- loss: the launch sequences behind pp_sparse_ce_(lowres_)(weighted_)fwd_bwd -------------------------------------------
+// One sequence per entry pair; WT = false is the un-weighted entry's (its kernels, its launch shapes), WT = true the weighted one's.
+constexpr size_t kCeWorkspaceBytes = 1024 * 2 * 4 + 256;
+
+// label_smoothing in [0, 1] (NaN fails the comparison too) -> what the kernels take
+static int ce_weights(const float* class_weight, float label_smoothing, int C, const char* what, CeW<true>& cw)
+{
+    if (!(label_smoothing >= 0.0f && label_smoothing <= 1.0f))
+        return fail(PP_ERR_BAD_ARG, "%s: label_smoothing=%f outside [0,1]", what, (double)label_smoothing);
+    cw.cw = class_weight;
+    cw.om = 1.0f - label_smoothing;
+    cw.sc = label_smoothing / (float)C;
+    return PP_OK;
+}
+
+template <bool WT>
+static int sparse_ce_launch(const float* logits, int B, int C, int64_t HW, int64_t sB, int64_t sC, const int64_t* target,
+                            int ignore_index, float* loss, float* count, const float* grad_out, float* dlogits, void* workspace,
+                            hipStream_t st, CeW<WT> cw)
+{
+    float* part = reinterpret_cast<float*>(workspace);
+    int nblk = (int)cdiv((int64_t)B * HW, kT * 8);
+    if (nblk > 1024) nblk = 1024;
+    if (nblk < 1) nblk = 1;
+    hipLaunchKernelGGL((ce_partial_kernel<WT>), dim3(nblk), dim3(kT), 0, st, logits, target, B, C, HW, sB, sC, ignore_index, part, cw);
+    if (int rc = check_launch(WT ? "ce_partial_kernel<weighted>" : "ce_partial_kernel")) return rc;
+    hipLaunchKernelGGL((ce_finalize_wave_kernel<WT>), dim3(1), dim3(64), 0, st, part, nblk, loss, count);
+    if (int rc = check_launch("ce_finalize_wave_kernel")) return rc;
+    if (dlogits) {
+        hipLaunchKernelGGL((ce_bwd_kernel<WT>), dim3(grid_for((int64_t)B * HW)), dim3(kT), 0, st, logits, target, B, C, HW, sB, sC,
+                           ignore_index, count, grad_out, dlogits, cw);
+        if (int rc = check_launch(WT ? "ce_bwd_kernel<weighted>" : "ce_bwd_kernel")) return rc;
+    }
+    return PP_OK;
+}
+
+template <bool WT>
+static int sparse_ce_lowres_launch(const float* low, int64_t ldx, int B, int C, int h, int w, int H, int W, float sh, float sw,
+                                   int align_corners, const int64_t* target, int ignore_index, float* loss, float* count, const float* grad_out,
+                                   float* dlow, int64_t lddx, void* workspace, hipStream_t st, CeW<WT> cw)
+{
+    const int al = align_corners ? 1 : 0;
+    float* part = reinterpret_cast<float*>(workspace);
+    int nblk = (int)cdiv((int64_t)B * H * W, kT * 8);
+    if (nblk > 1024) nblk = 1024;
+    if (nblk < 1) nblk = 1;
+    const unsigned gb = (unsigned)cdiv((int64_t)B * h * w, kT);
+    if (C > 64 || g_ce_stream) {   // any class count: the class vector is walked from memory (the workspace holds the block partials only)
+        hipLaunchKernelGGL((ce_lowres_stream_partial_kernel<WT>), dim3(nblk), dim3(kT), 0, st, low, ldx, B, C, h, w, H, W, sh, sw, al,
+                           target, ignore_index, part, cw);
+        if (int rc = check_launch(WT ? "ce_lowres_stream_partial_kernel<weighted>" : "ce_lowres_stream_partial_kernel")) return rc;
+        hipLaunchKernelGGL((ce_finalize_wave_kernel<WT>), dim3(1), dim3(64), 0, st, part, nblk, loss, count);
+        if (int rc = check_launch("ce_finalize_wave_kernel")) return rc;
+        if (dlow) {
+            const unsigned chunks = (unsigned)cdiv(C, kCeChunk);
+            if (chunks > 65535u) return fail(PP_ERR_UNSUPPORTED, "sparse_ce_lowres: C=%d", C);
+            hipLaunchKernelGGL((ce_lowres_stream_bwd_kernel<WT>), dim3(gb, chunks), dim3(kT), 0, st, low, ldx, B, C, h, w, H, W, sh, sw,
+                               al, target, ignore_index, count, grad_out, dlow, lddx, cw);
+            if (int rc = check_launch(WT ? "ce_lowres_stream_bwd_kernel<weighted>" : "ce_lowres_stream_bwd_kernel")) return rc;
+        }
+        return PP_OK;
+    }
+    return lowres_by_classes(C, [&](auto cmax, auto exact) -> int {
+        constexpr int CM = decltype(cmax)::value;
+        constexpr bool EX = decltype(exact)::value;
+        hipLaunchKernelGGL((ce_lowres_partial_kernel<CM, EX, WT>), dim3(nblk), dim3(kT), 0, st, low, ldx, B, C, h, w, H, W, sh, sw, al,
+                           target, ignore_index, part, cw);
+        if (int rc = check_launch(WT ? "ce_lowres_partial_kernel<weighted>" : "ce_lowres_partial_kernel")) return rc;
+        hipLaunchKernelGGL((ce_finalize_wave_kernel<WT>), dim3(1), dim3(64), 0, st, part, nblk, loss, count);
+        if (int rc = check_launch("ce_finalize_wave_kernel")) return rc;
+        if (dlow) {
+            hipLaunchKernelGGL((ce_lowres_bwd_kernel<CM, EX, WT>), dim3(gb), dim3(kT), 0, st, low, ldx, B, C, h, w, H, W, sh, sw, al,
+                               target, ignore_index, count, grad_out, dlow, lddx, cw);
+            if (int rc = check_launch(WT ? "ce_lowres_bwd_kernel<weighted>" : "ce_lowres_bwd_kernel")) return rc;
+        }
+        return PP_OK;
+    });
 }
 
 }  // namespace pp
@@ -3144,7 +3339,7 @@ int pp_dropout2d(const float* x, int64_t ldx, float* y, int64_t ldy, int B, int6
 }
 
 // ---- loss ----------------------------------------------------------------------------------------------------------
-size_t pp_sparse_ce_workspace_bytes(void) { return 1024 * 2 * 4 + 256; }
+size_t pp_sparse_ce_workspace_bytes(void) { return kCeWorkspaceBytes; }
 
 int pp_sparse_ce_fwd_bwd(const float* logits, int B, int C, int64_t HW, int64_t sB, int64_t sC, const int64_t* target,
                          int ignore_index, float* loss, float* count, const float* grad_out, float* dlogits, void* workspace,
@@ -3152,21 +3347,21 @@ int pp_sparse_ce_fwd_bwd(const float* logits, int B, int C, int64_t HW, int64_t 
 {
     if (!logits || !target || !loss || !count) return fail(PP_ERR_BAD_ARG, "sparse_ce: null");
     if (!workspace || ws_bytes < pp_sparse_ce_workspace_bytes()) return fail(PP_ERR_WORKSPACE, "sparse_ce: workspace");
-    hipStream_t st = as_stream(stream);
-    float* part = reinterpret_cast<float*>(workspace);
-    int nblk = (int)cdiv((int64_t)B * HW, kT * 8);
-    if (nblk > 1024) nblk = 1024;
-    if (nblk < 1) nblk = 1;
-    hipLaunchKernelGGL(ce_partial_kernel, dim3(nblk), dim3(kT), 0, st, logits, target, B, C, HW, sB, sC, ignore_index, part);
-    if (int rc = check_launch("ce_partial_kernel")) return rc;
-    hipLaunchKernelGGL(ce_finalize_wave_kernel, dim3(1), dim3(64), 0, st, part, nblk, loss, count);
-    if (int rc = check_launch("ce_finalize_wave_kernel")) return rc;
-    if (dlogits) {
-        hipLaunchKernelGGL(ce_bwd_kernel, dim3(grid_for((int64_t)B * HW)), dim3(kT), 0, st, logits, target, B, C, HW, sB, sC,
-                           ignore_index, count, grad_out, dlogits);
-        if (int rc = check_launch("ce_bwd_kernel")) return rc;
-    }
-    return PP_OK;
+    return sparse_ce_launch<false>(logits, B, C, HW, sB, sC, target, ignore_index, loss, count, grad_out, dlogits, workspace,
+                                   as_stream(stream), CeW<false>{});
+}
+
+int pp_sparse_ce_weighted_fwd_bwd(const float* logits, int B, int C, int64_t HW, int64_t sB, int64_t sC, const int64_t* target,
+                                  int ignore_index, const float* class_weight, float label_smoothing, float* loss, float* wsum,
+                                  const float* grad_out, float* dlogits, void* workspace, size_t ws_bytes, pp_stream_t stream)
+{
+    if (!logits || !target || !loss || !wsum) return fail(PP_ERR_BAD_ARG, "sparse_ce_weighted: null");
+    if (B < 1 || C < 1 || HW < 1) return fail(PP_ERR_BAD_ARG, "sparse_ce_weighted: bad shape B=%d C=%d HW=%lld", B, C, (long long)HW);
+    CeW<true> cw;
+    if (int rc = ce_weights(class_weight, label_smoothing, C, "sparse_ce_weighted", cw)) return rc;
+    if (!workspace || ws_bytes < pp_sparse_ce_workspace_bytes()) return fail(PP_ERR_WORKSPACE, "sparse_ce_weighted: workspace");
+    return sparse_ce_launch<true>(logits, B, C, HW, sB, sC, target, ignore_index, loss, wsum, grad_out, dlogits, workspace,
+                                  as_stream(stream), cw);
 }
 
 size_t pp_sparse_ce_lowres_workspace_bytes(void) { return pp_sparse_ce_workspace_bytes(); }
@@ -3180,53 +3375,29 @@ int pp_sparse_ce_lowres_fwd_bwd(const float* low, int64_t ldx, int B, int C, int
         return fail(PP_ERR_BAD_ARG, "sparse_ce_lowres: bad shape B=%d C=%d %dx%d -> %dx%d ldx=%lld lddx=%lld", B, C, h, w, H, W,
                     (long long)ldx, (long long)lddx);
     if (!workspace || ws_bytes < pp_sparse_ce_lowres_workspace_bytes()) return fail(PP_ERR_WORKSPACE, "sparse_ce_lowres: workspace");
-    hipStream_t st = as_stream(stream);
     float sh, sw;
     bil_scales(h, w, H, W, align_corners, 0.0f, 0.0f, sh, sw);
-    const int al = align_corners ? 1 : 0;
-    float* part = reinterpret_cast<float*>(workspace);
-    int nblk = (int)cdiv((int64_t)B * H * W, kT * 8);
-    if (nblk > 1024) nblk = 1024;
-    if (nblk < 1) nblk = 1;
-    const unsigned gb = (unsigned)cdiv((int64_t)B * h * w, kT);
-#define PP_CE_LOW(CM, EX)                                                                                                      \
-    do {                                                                                                                       \
-        hipLaunchKernelGGL((ce_lowres_partial_kernel<CM, EX>), dim3(nblk), dim3(kT), 0, st, low, ldx, B, C, h, w, H, W, sh, sw, al, \
-                           target, ignore_index, part);                                                                        \
-        if (int rc = check_launch("ce_lowres_partial_kernel")) return rc;                                                      \
-        hipLaunchKernelGGL(ce_finalize_wave_kernel, dim3(1), dim3(64), 0, st, part, nblk, loss, count);                        \
-        if (int rc = check_launch("ce_finalize_wave_kernel")) return rc;                                                       \
-        if (dlow) {                                                                                                            \
-            hipLaunchKernelGGL((ce_lowres_bwd_kernel<CM, EX>), dim3(gb), dim3(kT), 0, st, low, ldx, B, C, h, w, H, W, sh, sw, al, \
-                               target, ignore_index, count, grad_out, dlow, lddx);                                             \
-            if (int rc = check_launch("ce_lowres_bwd_kernel")) return rc;                                                      \
-        }                                                                                                                      \
-    } while (0)
-    if (C > 64 || g_ce_stream) {   // any class count: the class vector is walked from memory (the workspace holds the block partials only)
-        hipLaunchKernelGGL(ce_lowres_stream_partial_kernel, dim3(nblk), dim3(kT), 0, st, low, ldx, B, C, h, w, H, W, sh, sw, al, target,
-                           ignore_index, part);
-        if (int rc = check_launch("ce_lowres_stream_partial_kernel")) return rc;
-        hipLaunchKernelGGL(ce_finalize_wave_kernel, dim3(1), dim3(64), 0, st, part, nblk, loss, count);
-        if (int rc = check_launch("ce_finalize_wave_kernel")) return rc;
-        if (dlow) {
-            const unsigned chunks = (unsigned)cdiv(C, kCeChunk);
-            if (chunks > 65535u) return fail(PP_ERR_UNSUPPORTED, "sparse_ce_lowres: C=%d", C);
-            hipLaunchKernelGGL(ce_lowres_stream_bwd_kernel, dim3(gb, chunks), dim3(kT), 0, st, low, ldx, B, C, h, w, H, W, sh, sw, al,
-                               target, ignore_index, count, grad_out, dlow, lddx);
-            if (int rc = check_launch("ce_lowres_stream_bwd_kernel")) return rc;
-        }
-        return PP_OK;
-    }
-    switch (C) {
-        case 11: PP_CE_LOW(11, true); break;
-        case 19: PP_CE_LOW(19, true); break;
-        case 21: PP_CE_LOW(21, true); break;
-        default:
-            if (C <= 32) PP_CE_LOW(32, false);
-            else PP_CE_LOW(64, false);
-    }
-#undef PP_CE_LOW
-    return PP_OK;
+    return sparse_ce_lowres_launch<false>(low, ldx, B, C, h, w, H, W, sh, sw, align_corners, target, ignore_index, loss, count, grad_out, dlow,
+                                          lddx, workspace, as_stream(stream), CeW<false>{});
+}
+
+int pp_sparse_ce_lowres_weighted_fwd_bwd(const float* low, int64_t ldx, int B, int C, int h, int w, int H, int W, int align_corners,
+                                         const int64_t* target, int ignore_index, const float* class_weight, float label_smoothing,
+                                         float* loss, float* wsum, const float* grad_out, float* dlow, int64_t lddx, void* workspace,
+                                         size_t ws_bytes, pp_stream_t stream)
+{
+    if (!low || !target || !loss || !wsum) return fail(PP_ERR_BAD_ARG, "sparse_ce_lowres_weighted: null");
+    if (B < 1 || C < 1 || h < 1 || w < 1 || H < 1 || W < 1 || ldx < C || (dlow && lddx < C))
+        return fail(PP_ERR_BAD_ARG, "sparse_ce_lowres_weighted: bad shape B=%d C=%d %dx%d -> %dx%d ldx=%lld lddx=%lld", B, C, h, w, H,
+                    W, (long long)ldx, (long long)lddx);
+    CeW<true> cw;
+    if (int rc = ce_weights(class_weight, label_smoothing, C, "sparse_ce_lowres_weighted", cw)) return rc;
+    if (!workspace || ws_bytes < pp_sparse_ce_lowres_workspace_bytes())
+        return fail(PP_ERR_WORKSPACE, "sparse_ce_lowres_weighted: workspace");
+    float sh, sw;
+    bil_scales(h, w, H, W, align_corners, 0.0f, 0.0f, sh, sw);
+    return sparse_ce_lowres_launch<true>(low, ldx, B, C, h, w, H, W, sh, sw, align_corners, target, ignore_index, loss, wsum, grad_out, dlow,
+                                         lddx, workspace, as_stream(stream), cw);
 }
 
 // ---- optimiser ------------------------------------------------------------------------------------------------------

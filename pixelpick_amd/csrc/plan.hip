@@ -140,6 +140,8 @@ const Entry kEntries[] = {
     PP_PLAN_ENTRY(pp_aug_to_tensor),
     PP_PLAN_ENTRY(pp_sparse_ce_fwd_bwd),
     PP_PLAN_ENTRY(pp_sparse_ce_lowres_fwd_bwd),
+    PP_PLAN_ENTRY(pp_sparse_ce_weighted_fwd_bwd),
+    PP_PLAN_ENTRY(pp_sparse_ce_lowres_weighted_fwd_bwd),
     PP_PLAN_ENTRY(pp_confusion_matrix_update),
     PP_PLAN_ENTRY(pp_confusion_matrix_from_labels),
     PP_PLAN_ENTRY(pp_predict_lowres),

@@ -1813,51 +1813,88 @@ def _concat_bwd(tape: Tape, dy, parts):
 
 
 # ------------------------------------------------------------------------------------------------- loss
-def cross_entropy_nchw(logits: torch.Tensor, target: torch.Tensor, ignore_index: int, want_grad: bool = True, sparse: bool = True):
+def _ce_weight_args(class_weight, label_smoothing, C: int, dev):
+    """(class_weight pointer | None, label_smoothing, weighted?) of a loss call; ValueError before any launch for a weight vector that
+    is not a float32 tensor of C elements on `dev`, or a smoothing outside [0, 1]."""
+    eps = float(label_smoothing)
+    if not 0.0 <= eps <= 1.0:              # (NaN fails both comparisons)
+        raise ValueError(f"label_smoothing={label_smoothing} outside [0, 1]")
+    if class_weight is None:
+        return None, eps, eps != 0.0
+    if not isinstance(class_weight, torch.Tensor) or class_weight.device != dev:
+        raise ValueError(f"class_weight must be a tensor on {dev}")
+    if class_weight.dtype != torch.float32 or class_weight.dim() != 1 or class_weight.numel() != C or not class_weight.is_contiguous():
+        raise ValueError(f"class_weight must be a contiguous float32 vector of {C} elements, got {class_weight.dtype} "
+                         f"{tuple(class_weight.shape)}")
+    return class_weight.data_ptr(), eps, True
+
+
+def cross_entropy_nchw(logits: torch.Tensor, target: torch.Tensor, ignore_index: int, want_grad: bool = True, sparse: bool = True,
+                       class_weight: Optional[torch.Tensor] = None, label_smoothing: float = 0.0):
     """F.cross_entropy(logits [B,C,H,W], target [B,H,W] int64, ignore_index) -> (loss [1], dlogits | None).
     sparse: the caller knows that only a few pixels are labelled (model.py:108-110) - the gradient is marked so that the backward
-    behind it may skip its zero rows; False for densely labelled targets (every row would be flagged: the dense kernels are faster)."""
+    behind it may skip its zero rows; False for densely labelled targets (every row would be flagged: the dense kernels are faster).
+    class_weight (device float32 [C]) / label_smoothing: F.cross_entropy's weight= / label_smoothing= (pp_sparse_ce_weighted_fwd_bwd);
+    with both at their defaults the call is the un-weighted entry's, as it always was."""
     assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 4
     B, C, H, W = logits.shape
     assert logits.stride(3) == 1 and logits.stride(2) == W, "logits planes must be contiguous"
+    dev = logits.device
+    cw, eps, weighted = _ce_weight_args(class_weight, label_smoothing, C, dev)
     target = target.to(logits.device, torch.int64).contiguous()
     L = _lib.lib()
-    dev = logits.device
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     count = torch.empty(1, dtype=torch.float32, device=dev)
     dl = torch.empty((B, C, H, W), dtype=torch.float32, device=dev) if want_grad else None
     ws = _ws(_wsbytes("pp_sparse_ce_workspace_bytes"), dev)
-    rc = L.pp_sparse_ce_fwd_bwd(logits.data_ptr(), B, C, H * W, logits.stride(0), logits.stride(1), target.data_ptr(),
-                                int(ignore_index), loss.data_ptr(), count.data_ptr(), None,
-                                dl.data_ptr() if dl is not None else None, ws.data_ptr(), ws.numel(), _stream())
-    _lib.check(rc, "pp_sparse_ce_fwd_bwd")
+    if weighted:
+        rc = L.pp_sparse_ce_weighted_fwd_bwd(logits.data_ptr(), B, C, H * W, logits.stride(0), logits.stride(1), target.data_ptr(),
+                                             int(ignore_index), cw, eps, loss.data_ptr(), count.data_ptr(), None,
+                                             dl.data_ptr() if dl is not None else None, ws.data_ptr(), ws.numel(), _stream())
+        _lib.check(rc, "pp_sparse_ce_weighted_fwd_bwd")
+    else:
+        rc = L.pp_sparse_ce_fwd_bwd(logits.data_ptr(), B, C, H * W, logits.stride(0), logits.stride(1), target.data_ptr(),
+                                    int(ignore_index), loss.data_ptr(), count.data_ptr(), None,
+                                    dl.data_ptr() if dl is not None else None, ws.data_ptr(), ws.numel(), _stream())
+        _lib.check(rc, "pp_sparse_ce_fwd_bwd")
     if dl is not None and sparse:
         dl._pp_sparse_rows = True        # zero wherever target == ignore_index (model.py:113-119: all but the labelled pixels)
     return loss, dl
 
 
 def cross_entropy_lowres(low: torch.Tensor, size, target: torch.Tensor, ignore_index: int, align_corners: bool = True,
-                         want_grad: bool = True, sparse: bool = True):
+                         want_grad: bool = True, sparse: bool = True, class_weight: Optional[torch.Tensor] = None,
+                         label_smoothing: float = 0.0):
     """F.cross_entropy(F.interpolate(low, size, 'bilinear', align_corners), target, ignore_index) and its gradient w.r.t.
     `low`, without the full-size logits (deeplab.py:55-56 + model.py:116).  low [B,h,w,C] channels-last (the classifier
     output), target [B,H,W] int64 -> (loss [1], dlow [B,h,w,C] | None).  Any class count: up to 64 classes the kernels hold the
-    class vector in registers, wider heads stream it from memory (csrc/nn_ops.hip, ce_lowres_stream_*)."""
+    class vector in registers, wider heads stream it from memory (csrc/nn_ops.hip, ce_lowres_stream_*).
+    class_weight (device float32 [C]) / label_smoothing: F.cross_entropy's weight= / label_smoothing=
+    (pp_sparse_ce_lowres_weighted_fwd_bwd); with both at their defaults the call is the un-weighted entry's, as it always was."""
     assert low.is_cuda and low.dtype == torch.float32 and low.dim() == 4 and low.stride(3) == 1
     B, h, w, C = low.shape
     assert low.stride(1) == w * low.stride(2) and low.stride(0) == h * low.stride(1)
     H, W = int(size[0]), int(size[1])
+    dev = low.device
+    cw, eps, weighted = _ce_weight_args(class_weight, label_smoothing, C, dev)
     target = target.to(low.device, torch.int64).contiguous()
     assert tuple(target.shape) == (B, H, W)
-    dev = low.device
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     count = torch.empty(1, dtype=torch.float32, device=dev)
     dlow = torch.empty((B, h, w, C), dtype=torch.float32, device=dev) if want_grad else None
     ws = _ws(_wsbytes("pp_sparse_ce_lowres_workspace_bytes"), dev)
-    rc = _lib.lib().pp_sparse_ce_lowres_fwd_bwd(low.data_ptr(), low.stride(2), B, C, h, w, H, W, int(bool(align_corners)),
-                                                target.data_ptr(), int(ignore_index), loss.data_ptr(), count.data_ptr(), None,
-                                                dlow.data_ptr() if dlow is not None else None, C, ws.data_ptr(), ws.numel(),
-                                                _stream())
-    _lib.check(rc, "pp_sparse_ce_lowres_fwd_bwd")
+    if weighted:
+        rc = _lib.lib().pp_sparse_ce_lowres_weighted_fwd_bwd(low.data_ptr(), low.stride(2), B, C, h, w, H, W, int(bool(align_corners)),
+                                                             target.data_ptr(), int(ignore_index), cw, eps, loss.data_ptr(),
+                                                             count.data_ptr(), None, dlow.data_ptr() if dlow is not None else None,
+                                                             C, ws.data_ptr(), ws.numel(), _stream())
+        _lib.check(rc, "pp_sparse_ce_lowres_weighted_fwd_bwd")
+    else:
+        rc = _lib.lib().pp_sparse_ce_lowres_fwd_bwd(low.data_ptr(), low.stride(2), B, C, h, w, H, W, int(bool(align_corners)),
+                                                    target.data_ptr(), int(ignore_index), loss.data_ptr(), count.data_ptr(), None,
+                                                    dlow.data_ptr() if dlow is not None else None, C, ws.data_ptr(), ws.numel(),
+                                                    _stream())
+        _lib.check(rc, "pp_sparse_ce_lowres_fwd_bwd")
     if dlow is not None and _SPARSE_ROWS and sparse:
         # 20 labelled pixels per image (model.py:113-119) touch <= 4 low-resolution rows each: the gradient is zero in all other rows.
         # The flags ride on the tensor; the classifier's backward-data and the BatchNorm backward behind it skip the zero rows.

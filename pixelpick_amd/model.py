@@ -25,7 +25,7 @@ import torch.nn.functional as F
 from . import acquisition as acq
 from . import dist_utils
 from .query import QuerySelector
-from .trainer import FlatTrainer
+from .trainer import FlatTrainer, check_loss_options
 from .utils.metrics import AverageMeter, RunningScore
 from .utils.utils import Visualiser, get_model, optimizer_spec
 
@@ -79,6 +79,11 @@ class Model:
         self.init_n_pixels = args.n_init_pixels
         self.max_budget = args.max_budget
         self.n_classes = args.n_classes
+        # F.cross_entropy's weight= / label_smoothing= for every round's trainer (args.class_weight: n_classes numbers, absent / None =
+        # off; args.label_smoothing: absent / None / 0 = off).  The driver computes no weights itself: utils.balanced_class_weights turns
+        # QueryStats.dict_label_cnt or a data set's published class frequencies into them.
+        self.class_weight, self.label_smoothing = check_loss_options(getattr(args, "class_weight", None),
+                                                                     getattr(args, "label_smoothing", None) or 0.0, args.n_classes)
         self.n_epochs = args.n_epochs
         self.n_pixels_by_us = args.n_pixels_by_us
         self.network_name = args.network_name
@@ -292,7 +297,8 @@ class Model:
         model = get_model(self.args).to(self.device)
         kind, slow_lr, lr, wd, momentum = optimizer_spec(self.args)          # utils/utils.py:112-306, quirks included
         trainer = FlatTrainer(model, lr=lr, slow_lr=slow_lr, weight_decay=wd, optimizer=kind, momentum=momentum,
-                              ignore_index=self.ignore_index, sparse_labels=self.n_pixels_by_us != 0)
+                              ignore_index=self.ignore_index, sparse_labels=self.n_pixels_by_us != 0,
+                              class_weight=self.class_weight, label_smoothing=self.label_smoothing, n_classes=self.n_classes)
         n_total = self.n_epochs * self._steps_per_epoch()
         try:
             for e in range(1, 1 + self.n_epochs):

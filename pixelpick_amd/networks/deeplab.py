@@ -75,6 +75,7 @@ class DeepLab(nn.Module):
 
     def __init__(self, args, backbone='mobilenet', output_stride=16):
         super().__init__()
+        self.n_classes = int(args.n_classes)      # width of the head: what FlatTrainer checks class_weight against
         self._resnet = backbone == 'resnet'
         if self._resnet:
             from .backbones.resnet_backbone import ResNetBackbone

@@ -53,6 +53,7 @@ class FPNSeg(nn.Module):
 
     def __init__(self, args, load_pretrained=True):
         super().__init__()
+        self.n_classes = int(args.n_classes)      # width of the head: what FlatTrainer checks class_weight against
         self.encoder = Encoder(args, load_pretrained)
         self.decoder = FPNDecoder(args)
         self._last_emb = None

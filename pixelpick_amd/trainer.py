@@ -8,9 +8,18 @@ backbone first, so the two learning-rate groups are two contiguous segments.
 
 Data-parallel semantics: one process per GPU, per-GPU batch and per-GPU BatchNorm
 statistics (the reference has no SyncBN), gradients averaged over ranks.  Nothing else crosses GPUs.
-"""
-from typing import Optional
+The loss is normalised per rank ("loss normalisation subtlety"): F.cross_entropy means over the LOCAL labelled
+pixels, and with class weights over the local weight sum Wsum - what torch DistributedDataParallel computes as well.  Ranks whose
+batches hold different classes therefore normalise by different sums; the gradient all-reduce is the plain average either way.
 
+Class imbalance (FlatTrainer(class_weight=, label_smoothing=)): F.cross_entropy's `weight=` and `label_smoothing=` on the
+device - pp_sparse_ce_(lowres_)weighted_fwd_bwd in place of the un-weighted loss entry, the weights uploaded once and kept for
+the life of the trainer so that a recorded step replays against them.  Off (None, 0.0) the step is the un-weighted one, launch
+for launch.
+"""
+from typing import Optional, Sequence
+
+import math
 import os
 
 import torch
@@ -32,6 +41,36 @@ FORCE_COLLECTIVES = os.environ.get("PIXELPICK_FORCE_COLLECTIVES", "0") == "1"
 NATIVE_PLAN = os.environ.get("PIXELPICK_NATIVE_PLAN", "1") != "0"
 
 
+def check_loss_options(class_weight, label_smoothing, n_classes: Optional[int] = None):
+    """Host-side validation of FlatTrainer's loss options (no device needed): class_weight None or `n_classes` finite,
+    non-negative numbers (a sequence or a tensor), label_smoothing in [0, 1).  Returns (list of floats | None, float);
+    ValueError otherwise."""
+    try:
+        eps = float(label_smoothing)
+    except (TypeError, ValueError):
+        raise ValueError(f"label_smoothing must be a number, got {label_smoothing!r}")
+    if not 0.0 <= eps < 1.0:                       # (NaN fails both comparisons)
+        raise ValueError(f"label_smoothing={label_smoothing} outside [0, 1)")
+    if class_weight is None:
+        return None, eps
+    if isinstance(class_weight, torch.Tensor):
+        if class_weight.dim() != 1:
+            raise ValueError(f"class_weight must be one-dimensional, got shape {tuple(class_weight.shape)}")
+        class_weight = class_weight.detach().double().cpu().tolist()
+    try:
+        w = [float(v) for v in class_weight]
+    except (TypeError, ValueError):
+        raise ValueError("class_weight must be a sequence of numbers")
+    if n_classes is not None and len(w) != int(n_classes):
+        raise ValueError(f"class_weight has {len(w)} elements for {n_classes} classes")
+    if not w:
+        raise ValueError("class_weight is empty")
+    for c, v in enumerate(w):
+        if not math.isfinite(v) or v < 0.0:
+            raise ValueError(f"class_weight[{c}]={v} must be finite and non-negative")
+    return w, eps
+
+
 _RESERVE = {"users": 0, "before": None}     # collective trainers alive in this process / the library's reserve before the first of them
 
 
@@ -50,12 +89,22 @@ def default_comm_cu_reserve(backend: str) -> int:
 class FlatTrainer:
     def __init__(self, model, lr: float = 5e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 2e-4,
                  ignore_index: int = 19, slow_module_names=("backbone", "encoder"), process_group=None,
-                 optimizer: str = "adam", momentum: float = 0.9, slow_lr: float = None, sparse_labels: bool = True):
+                 optimizer: str = "adam", momentum: float = 0.9, slow_lr: float = None, sparse_labels: bool = True,
+                 class_weight: Optional[Sequence[float]] = None, label_smoothing: float = 0.0, n_classes: Optional[int] = None):
         """optimizer "adam": torch.optim.Adam(lr/10 for the backbone|encoder, lr for the rest) - what the reference builds for
         cs / cv (utils/utils.py:114-141; NOTE it passes only lr and weight_decay to Adam, so betas/eps are torch's defaults
         (0.9, 0.999), 1e-8 whatever args.optimizer_params says).  "sgd": torch.optim.SGD(momentum) with `slow_lr` for the
-        backbone|encoder (default lr/10) - voc and optimizer_type "SGD" (utils/utils.py:208-270)."""
+        backbone|encoder (default lr/10) - voc and optimizer_type "SGD" (utils/utils.py:208-270).
+        class_weight (None, or n_classes finite non-negative numbers) / label_smoothing (in [0, 1)): F.cross_entropy's weight= and
+        label_smoothing= for the step's loss.  n_classes: the width of the model's head, what the length of class_weight is held to here
+        on the host; default `model.n_classes` (DeepLab and FPNSeg state it).  A model that does not state it needs the argument:
+        class_weight without a known class count is a ValueError, never a check deferred to the first step."""
         assert optimizer in ("adam", "sgd")
+        if n_classes is None:
+            n_classes = getattr(model, "n_classes", None)
+        if class_weight is not None and n_classes is None:
+            raise ValueError("class_weight needs the class count: pass n_classes= or give the model an n_classes attribute")
+        weights, self.label_smoothing = check_loss_options(class_weight, label_smoothing, n_classes)
         self.model = model
         self.optimizer, self.momentum = optimizer, momentum
         self.slow_lr = lr / 10 if slow_lr is None else slow_lr
@@ -135,6 +184,8 @@ class FlatTrainer:
             src = torch.distributed.get_global_rank(self.pg, 0) if self.pg is not None else 0
             torch.distributed.broadcast(self.flat_p, src=src, group=self.pg)
             self.sync_buffers()
+        # uploaded once, never reallocated: a recorded plan holds this address
+        self.class_weight = None if weights is None else torch.tensor(weights, dtype=torch.float64).to(torch.float32).to(dev)
         self.step_count = 0
         self.lr_factor = 1.0
         self.last_loss: Optional[torch.Tensor] = None
@@ -183,7 +234,8 @@ class FlatTrainer:
             low, _ = self.model._run(tape, x, upsample=False)
             size = tuple(x.shape[2:])
             align = bool(getattr(self.model, "LOWRES_ALIGN_CORNERS", True))     # DeepLab: align_corners=True x4; FPNSeg: False, x2
-            loss, dlow = E.cross_entropy_lowres(low.t, size, y, self.ignore_index, align_corners=align, sparse=self.sparse_labels)
+            loss, dlow = E.cross_entropy_lowres(low.t, size, y, self.ignore_index, align_corners=align, sparse=self.sparse_labels,
+                                                    class_weight=self.class_weight, label_smoothing=self.label_smoothing)
             if keep_logits == "low":
                 # the step metrics interpolate the classifier output themselves (RunningScore.update_from_lowres): no
                 # full-resolution E.bilinear in this mode
@@ -199,7 +251,8 @@ class FlatTrainer:
                 raise ValueError('keep_logits="low" needs a model whose logits are interpolated from its classifier output '
                                  '(LOWRES_LOGITS) and the low-resolution loss path')
             pred, _ = self.model._run(tape, x)
-            loss, dlogits = E.cross_entropy_nchw(pred.t, y, self.ignore_index, sparse=self.sparse_labels)
+            loss, dlogits = E.cross_entropy_nchw(pred.t, y, self.ignore_index, sparse=self.sparse_labels, class_weight=self.class_weight,
+                                                    label_smoothing=self.label_smoothing)
             self.last_low = None
             self.last_logits = pred.t if keep_logits else None
             tape.backward(pred, dlogits)

@@ -34,6 +34,24 @@ def optimizer_spec(args):
     return "adam", op['lr'] / 10, op['lr'], op['weight_decay'], 0.0
 
 
+def balanced_class_weights(counts):
+    """Per-class loss weights from label counts (QueryStats.dict_label_cnt's values in class order, or a data set's published
+    class frequencies): n_total / (K * n_c) for the K classes with n_c > 0 - the weights average 1 over the labels counted, so
+    the loss keeps its scale - and 1.0 for a class with no count.  float64 on the host; returns a list for
+    FlatTrainer(class_weight=) / args.class_weight.  A mapping is read by class index (missing classes count 0)."""
+    if isinstance(counts, dict):
+        n = (max(int(k) for k in counts) + 1) if counts else 0
+        counts = [counts.get(c, 0) for c in range(n)]
+    c = np.asarray(list(counts), dtype=np.float64).reshape(-1)
+    if not np.all(np.isfinite(c)) or np.any(c < 0):
+        raise ValueError("balanced_class_weights: counts must be finite and non-negative")
+    seen = c > 0
+    w = np.ones_like(c)
+    if seen.any():
+        w[seen] = c.sum() / (float(seen.sum()) * c[seen])
+    return w.tolist()
+
+
 def _param_groups(args, model, slow_lr, lr, weight_decay, extra):
     if args.network_name == "FPN":
         parts = [(model.encoder, slow_lr), (model.decoder, lr)]
